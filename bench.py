@@ -11,8 +11,12 @@ The K timed steps are split over the three loops in those proportions (A, B, C b
 Synthetic inputs and random-init weights (no datasets / checkpoints offline), all resident in HBM before the timed
 region.  bf16 operands, fp32 accumulation / residual / LayerNorm / softmax.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything measured beside the headline
+(`roofline`, `kernels`, `extra`, `cpu_baseline`: other loops, precisions and configurations, per-kernel passes, the CPU legs; minutes).
+--dump-outputs DIR writes the latents the timed steps left (float32 .npy) for output-by-output comparison of two builds.
 
 N > 1: one process per GPU, the batch is sharded by rank (512 samples per rank: weak scaling), no data-path
 collective; the finished latents are collected with ONE all_gather (RCCL) inside the timed region.
@@ -565,14 +569,36 @@ def pmc_traffic(kernel, launches_per_step):
     return row["bytes_per_launch"], row.get("measured_on")
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write every tensor of `arrays` as path/<name>.npy in float32.  Above DUMP_BYTES in all, each array keeps the same fixed,
+    seeded sample of its leading-dimension rows (sorted), scaled to fit."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    total = sum(4 * v.numel() for v in host.values())
+    for name, v in host.items():
+        if total > DUMP_BYTES:
+            keep = max(1, v.shape[0] * DUMP_BYTES // total)
+            rows = torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v[rows]
+        np.save(os.path.join(path, name + ".npy"), v.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the measurements reported beside the headline")
+    ap.add_argument("--full", action="store_true", help="also run every measurement reported beside the headline (roofline / "
+                                                        "per-kernel pass, extra, CPU baselines); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write the latents they left as DIR/<name>.npy "
+                                                          "(float32; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline pass")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the measurements reported in `extra`")
     ap.add_argument("--dry-run", action="store_true", help="launch + rendezvous + JSON only, on CPU (no compute)")
     ap.add_argument("--dense", action="store_true", help="run every padded position of loop C like the reference (no compaction)")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even at world size 1 "
@@ -580,6 +606,11 @@ def main():
     ap.add_argument("--split", type=int, default=0, help="sample groups run concurrently on forked streams (0 = the "
                                                          "module's default: 2 at this batch size; 1 = off)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    run_extra = args.full and not args.no_extra
+    run_roofline = args.full and not args.no_roofline
+    run_cpu_baseline = args.full and not args.no_cpu_baseline
 
     ap_world = os.environ.get("WORLD_SIZE")
     if ap_world is None and args.gpus > 1:
@@ -664,6 +695,9 @@ def main():
         every = [torch.zeros(1, device=dev, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(every, torch.tensor([my_elapsed], device=dev, dtype=torch.float64))
         per_rank_ms = [round(1e3 * float(v) / args.steps, 4) for v in every]
+    if args.dump_outputs and rank == 0:
+        # what the timed steps handed back: the loop B / C latents (all ranks' rows when gathered) and this rank's loop A latents
+        dump_outputs(args.dump_outputs, {"loopA_surfPos": ldm.x["A"], "loopB_surfPos": out["surfPos"], "loopC_surfZ": out["surfZ"]})
     finite = all(bool(torch.isfinite(v).all()) for v in out.values())
     flops_cache = ldm.flops(ka, kb, kc)
 
@@ -676,7 +710,7 @@ def main():
         return time.perf_counter() - t1
 
     extra = {}
-    if not args.no_extra:
+    if run_extra:
         # each loop on its own (20 iterations), never part of `value`
         legs = {}
         for (key, what, w), ks in zip(LEGS, ((20, 0, 0), (0, 20, 0), (0, 0, 20))):
@@ -720,7 +754,7 @@ def main():
 
     roofline = None
     breakdown = None
-    if not args.no_roofline:
+    if run_roofline:
         # second pass of the same K steps with a hipEvent pair around every kernel launch (on the launch stream).  The
         # launches are serialised for it (n_split = 1): with two sample groups in flight every launch shares the CUs with
         # a launch of the other group, and its duration then says nothing about the kernel.
@@ -775,7 +809,7 @@ def main():
             roofline["all_16bit_gemm_kernels"] = {"tflops": round(fl / ms / 1e9, 1), "frac": round(fl / ms / 1e9 / MFMA_PEAK_TFLOPS, 4),
                                                   "ms_per_step": round(ms / args.steps, 4)}
 
-    if world == 1 and rank == 0 and not args.no_extra:
+    if world == 1 and rank == 0 and run_extra:
         try:
             extra["face_ldm_full_pass"] = face_ldm_full_pass_extra(ldm, dev, barrier)
         except Exception as e:
@@ -807,7 +841,7 @@ def main():
         line = {
             "metric": "denoising-steps/sec (whole node), DeepCAD face-LDM, batch=512",
             "value": round(steps_per_s, 3), "unit": "denoising-steps/s (batch=512 per step)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "value_dense": (round(world * extra["dense_definition_composite"]["steps_per_s_per_gpu"], 3)
                             if "dense_definition_composite" in extra else None),
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
@@ -833,9 +867,9 @@ def main():
                                         "fused input embeds; conditioning cache off (every embed recomputed)"},
             "roofline": roofline, "kernels": breakdown, "extra": extra,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and run_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
-            if not args.no_extra:
+            if run_extra:
                 # (GPU side of the same configurations: extra.cascade_cfg3 / rank_local_cfg4 / rank_local_cfg5, measured above)
                 try:
                     st = cpu_stage_baselines(line["cpu_baseline"]["threads"])

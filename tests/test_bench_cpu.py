@@ -48,3 +48,42 @@ def test_every_tool_script_compiles():
     assert len(files) >= 20
     for f in files:
         compile(open(f).read(), f, "exec")
+
+
+def test_full_and_dump_outputs_options():
+    """A plain run times the headline alone; --full adds the side measurements, --dump-outputs writes the timed path's latents.
+    --steps sets the number of timed steps, so a run without any is refused."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, env=_env(), timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout + r.stderr
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], capture_output=True, text=True,
+                       env=_env(), timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_split_steps_sums_to_steps():
+    sys.path.insert(0, ROOT)
+    import bench
+    for k in range(1, 1000):
+        ka, kb, kc = bench.split_steps(k)
+        assert ka + kb + kc == k and min(ka, kb, kc) >= 0
+        if k >= 3:
+            assert min(ka, kb, kc) >= 1
+
+
+def test_dump_outputs_float32_and_capped(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    small = {"a": torch.randn(3, 4, dtype=torch.bfloat16), "b": torch.arange(6.0, dtype=torch.float64).reshape(2, 3)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v.float().numpy())
+    big = {"x": torch.randn(6000, 60, 48), "y": torch.randn(6000, 60, 6)}      # 77.8 MB: sampled down to the cap
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    x1, y1 = np.load(tmp_path / "big1" / "x.npy"), np.load(tmp_path / "big1" / "y.npy")
+    assert 0 < x1.nbytes + y1.nbytes <= bench.DUMP_BYTES and x1.shape[0] == y1.shape[0] < 6000
+    assert np.array_equal(x1, np.load(tmp_path / "big2" / "x.npy"))            # the sample is fixed
+    assert any(np.array_equal(x1[0], r) for r in big["x"].numpy()[:x1.shape[0] + 1000])

@@ -15,7 +15,7 @@ if [[ $WHAT == all || $WHAT == test ]]; then
   tail -3 $O/pytest_gpu.log; tail -2 $O/smoke.log
 fi
 if [[ $WHAT == all || $WHAT == bench ]]; then
-  timeout 1500 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
+  timeout 1500 python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?" >> $O/bench.log
   tail -2 $O/bench.log | cut -c1-260
 fi
 if [[ $WHAT == all || $WHAT == prof ]]; then
@@ -65,8 +65,8 @@ if [[ $WHAT == all || $WHAT == vaeprof ]]; then
   timeout 300 python tools/vae_concurrent_bench.py > $O/vae_concurrent_bench.log 2>&1
 fi
 if [[ $WHAT == driver ]]; then
-  # the command the driver runs at round end
-  timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.log 2>&1; echo "bench rc=$?" >> $O/bench_driver_cmd.log
+  # the headline command at 20 + 5 steps, with every measurement reported beside it (--full: the line README.md quotes)
+  timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.log 2>&1; echo "bench rc=$?" >> $O/bench_driver_cmd.log
   tail -2 $O/bench_driver_cmd.log | cut -c1-260
 fi
 du -ah $O | sort -h | tail -30 > $O/listing.txt 2>&1
