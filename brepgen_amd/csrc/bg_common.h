@@ -7,7 +7,7 @@
 
 namespace bg {
 
-// ---- error plumbing (thread-local message behind bg_last_error) ---------------------------------
+// ---- error plumbing (thread-local message behind bg_last_error; runtime.hip, like the profiler and the bg_tune table below) ----
 void set_error(const char* fmt, ...);
 int launch_status(const char* what);   // hipGetLastError -> 0 / positive hipError_t (+message)
 
@@ -155,6 +155,27 @@ struct GemmArgs {
     int p256_stagger = 0;             // split-residual launches of the 256 x 256 kernel: start delay of the second phase group, x 1024 cycles
     int concurrent = 0;               // caller's hint: other launches of the same kind are in flight on sibling streams
 };
+
+// ---- GemmArgs by name (host side).  The struct is the kernels' kernarg: its layout is fixed, and `linear` is the only place that
+// fills it positionally; every launch says the rest in words. ----
+// out [M, N] (ldc) = act(a [M, K] (lda) . w [N_pad, K]^T + bias), out_dtype = BG_F32 or the operand dtype: the plain nn.Linear
+inline GemmArgs linear(const void* a, int lda, const void* w, const float* bias, void* out, int ldc, int M, int N, int N_pad, int K,
+                       int out_dtype, int act = BG_ACT_NONE) {
+    return GemmArgs{a, lda, w, bias, out, ldc, M, N, N_pad, K, out_dtype, act, nullptr, 0, 1};
+}
+// + add[row / div] (fp32 rows of ld floats; a null addend is none)
+inline void add_rows(GemmArgs& g, const float* add, int ld, int div) { g.add = add; g.ld_add = ld; g.add_div = add ? div : 1; }
+inline void add2_rows(GemmArgs& g, const float* add2, int ld, int div) { g.add2 = add2; g.ld_add2 = ld; g.add2_div = add2 ? div : 1; }
+// the result goes out as the split pair (g.out = hi, lo), with the rows' LayerNorm partials to `stats` (null = none)
+inline void split_out(GemmArgs& g, void* lo, float* stats) { g.out_lo = lo; g.stats_out = stats; }
+// + the split residual rows hi + lo (ld elements apart)
+inline void split_residual_in(GemmArgs& g, const void* hi, const void* lo, int ld) { g.res_hi = hi; g.res_lo = lo; g.ld_res = ld; }
+// `a` holds raw rows, w / bias / colsum the folded LayerNorm: normalised in the epilogue from the partials in `stats`
+inline void ln_fold_in(GemmArgs& g, const float* stats, const float* colsum) { g.stats_in = stats; g.colsum = colsum; }
+// compact rows: addend / output rows are looked up through row_map where the flag says so
+inline void map_rows(GemmArgs& g, const int* row_map, bool add, bool add2, bool out) {
+    g.row_map = row_map; g.map_add = add; g.map_add2 = add2; g.map_out = out;
+}
 
 // Tile-round quantisation: one 256 x 256 tile per CU and round, so a launch whose tile count is a little
 // above a multiple of 256 would spend a whole round on a few tiles.  The 256 kernel therefore takes the whole row panels that

@@ -1,59 +1,13 @@
 // Whole-net forward of the four BrepGen denoisers (network.py:1107-1126, 1176-1200, 1257-1286, 1357-1393),
 // enqueued on one stream from ONE C-ABI call: batch-first [M = B*N, 768] layout end to end (the reference's
-// seq-first permutes -- 38 % of its CPU time -- do not exist here), fp32 residual stream, activations in the
-// compute dtype, step-invariant conditioning embeds cached across denoising steps.
+// seq-first permutes -- 38 % of its CPU time -- do not exist here), residual stream in fp32 (fp32 mode, unfolded weights) or as a
+// split pair of 16-bit planes with the LayerNorms folded into the next GEMM (16-bit modes), activations in the compute dtype,
+// step-invariant conditioning embeds cached across denoising steps.  run() is the call, stage by stage; bg_embed_mlp_fwd and
+// bg_encoder_layer_fwd expose two of its pieces.  (Error plumbing, bg_tune and the profiler: runtime.hip.)
 #include "bg_common.h"
-#include <stdarg.h>
-#include <stdio.h>
 #include <mutex>
 
 namespace bg {
-
-static thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int launch_status(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return (int)e;
-}
-
-int g_tune[TUNE_COUNT] = {0};
-
-// ---- per-kernel event timing ------------------------------------------------------------------------------
-bool g_prof_on = false;
-namespace {
-struct ProfRec { hipEvent_t e0, e1; int kernel; double flops, bytes; };
-ProfRec* g_recs = nullptr;
-int g_cap = 0, g_n = 0;
-bool g_open = false;
-const char* const kProfNames[PK_COUNT] = {"gemm16_persistent_kernel(128x128)", "gemm16_kernel(generic: 128x64 / 64x64 tiles)", "gemm_f32", "attn16_kernel", "attn_f32_kernel",
-                                          "ln768_kernel", "ddpm_step_kernel", "pndm_step_kernel", "misc", "embed_ln_silu_kernel", "gemm16_p256_kernel(256x256)",
-                                          "gemm16_split_pipe_kernel(128x128)", "gemm16_p256_kernel(256x256, split-residual launches)",
-                                          "qkv_attn_kernel(256x192 + attention)", "ln_silu_out_kernel", "ffn_fused_kernel(64-row panels)"};
-}  // namespace
-
-void prof_pre(hipStream_t s) {
-    g_open = false;
-    if (g_n >= g_cap) return;
-    if (hipEventRecord(g_recs[g_n].e0, s) == hipSuccess) g_open = true;
-}
-
-void prof_post(int kernel, double flops, double bytes, hipStream_t s) {
-    if (!g_open) return;
-    g_open = false;
-    ProfRec& r = g_recs[g_n];
-    if (hipEventRecord(r.e1, s) != hipSuccess) return;
-    r.kernel = kernel; r.flops = flops; r.bytes = bytes;
-    ++g_n;
-}
 
 __global__ void expand_mask_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, size_t n, int E) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -122,63 +76,141 @@ struct Ctx {
     const int* offsets = nullptr;     // per-sample first row, [B+1]
     const int* rule = nullptr;        // 256 / 128 kernel partition of the GEMM launches for this row count (compact.hip)
     const int* slot_desc = nullptr;   // slot-packed batch: (n_a, n_b) per 64-row slot (compact_rows_paired)
-    int N_tok = 1;                    // tokens per sample of the padded layout
     double rows_hint = 0.0, pairs_hint = 0.0;   // host-side estimates: GEMM kernel choice + profiler accounting (brepgen_hip.h)
     double rows_plan = 0.0;                     // the row count the caller knows exactly (0 = not): launch plan only
     int concurrent = 0;               // sibling sample groups are in flight on forked streams (n_split > 1)
+    // the call: B samples of N tokens, M = row bound of every token-wise launch (the stand-alone pieces set what they use)
+    const bg_denoiser_inputs* in = nullptr;
+    int net = 0, B = 0, N = 1, E = 1, M = 0;
+    bool varlen = false;              // the valid tokens run compacted
+    bool paired = false;              // ... in 64-row slots of one or two samples, through the fused QKV / attention launch
+    bool fused_qkv = false;           // dense run: QKV + attention as one launch
+    const uint8_t* key_pad = nullptr; // [B, N] key-padding mask of the attention launches (null: every row is a valid key)
+    float* cvec = nullptr;            // [B, 768] time (+ class) embedding per sample
 };
 
-// Linear(k,768)+b -> LN -> SiLU -> Linear(768,n)+b (+adds) ; x fp32 rows (lda), or activations in compute dtype for fc_out
-// `to_stream`: the result goes to the token stream X -- fp32 rows (out = c.X, and add == c.X accumulates), or, in
+// The row count of a token-wise GEMM -- all five fields, set here and nowhere else.  Forgetting one still computes the right
+// result (every launch plan is correct for any row count) on a different kernel plan, which no parity test sees.
+// launch_plan = false: the count and its estimate only -- the embed MLPs' GEMMs, whose kernel choice has never looked at the rest.
+static void token_rows(const Ctx& c, GemmArgs& g, bool launch_plan = true) {
+    g.m_dev = c.m_dev; g.rows_hint = c.rows_hint;
+    if (launch_plan) { g.rule_table = c.rule; g.rows_plan = c.rows_plan; g.concurrent = c.concurrent; }
+}
+
+struct Addend { const float* rows = nullptr; int ld = 0; int div = 1; };   // fp32 rows [*, ld]: output row r adds rows[r / div]
+// TO_STREAM: the result goes to the token stream X -- fp32 rows (out = c.X, and add == c.X accumulates), or, in
 // fold mode, the split pair (XH, XL) with row statistics (accumulating = the stream is the addend)
-// `tok`: the rows are tokens.  In a variable-length run they are the COMPACT rows (count on the device): the inputs are
-// gathered through c.src_row, the broadcast addends are looked up through it (map_add: `add` is indexed by the padded
-// token index / add_div; map_add2 likewise), and with `scatter` the result rows go back to the padded layout.
-static int embed_mlp(Ctx& c, const bg_mlp_weights& m, const void* x, int lda, int rows, float* out, int ldc,
-                     const float* add, int ld_add, int add_div, const float* add2, int ld_add2, int add2_div,
-                     bool to_stream = false, bool tok = false, bool gather = false, bool map_add = false,
-                     bool map_add2 = false, bool scatter = false) {
+// TOK: the rows are tokens.  In a variable-length run they are the COMPACT rows (count on the device): with GATHER the inputs
+// are gathered through c.src_row, with MAP_ADD / MAP_ADD2 that broadcast addend is looked up through it (indexed by the padded
+// token index / div), and with SCATTER the result rows go back to the padded layout.
+enum EmbedOpt : unsigned { TO_STREAM = 1, TOK = 2, GATHER = 4, MAP_ADD = 8, MAP_ADD2 = 16, SCATTER = 32 };
+
+// Linear(k,768)+b -> LN -> SiLU -> Linear(768,n)+b (+adds) ; x fp32 rows (lda), or activations in compute dtype for fc_out
+static int embed_mlp(Ctx& c, const bg_mlp_weights& m, const void* x, int lda, int rows, float* out, int ldc, Addend add = {},
+                     Addend add2 = {}, unsigned opt = 0) {
     int rc;
-    const bool vl = tok && c.m_dev != nullptr;
-    const int* m_dev = vl ? c.m_dev : nullptr;
-    const double hint = vl ? c.rows_hint : 0.0;
+    const bool vl = (opt & TOK) && c.m_dev != nullptr;
     if (m.w0_mfma && m.w0_dtype == BG_F32 && embed_ln_silu_supported(m.k_in)) {
         // input embeds (k = 6 / 12 / 48): Linear + LayerNorm + SiLU in one kernel, nothing but the result written
         rc = embed_ln_silu(reinterpret_cast<const float*>(x), lda, rows, m.k_in, m.w0_mfma, m.b0, m.ln_g, m.ln_b, c.H,
-                           c.dtype, 1e-5f, c.s, m_dev, (vl && gather) ? c.src_row : nullptr, hint);
+                           c.dtype, 1e-5f, c.s, vl ? c.m_dev : nullptr, (vl && (opt & GATHER)) ? c.src_row : nullptr, vl ? c.rows_hint : 0.0);
         if (rc) return rc;
     } else {
-        BG_REQUIRE(!(vl && gather), BG_E_ARG, "bg_denoiser_fwd: variable-length execution needs the fused input embeds (w0_mfma)");
+        BG_REQUIRE(!(vl && (opt & GATHER)), BG_E_ARG, "bg_denoiser_fwd: variable-length execution needs the fused input embeds (w0_mfma)");
         float* t0 = reinterpret_cast<float*>(c.R);
-        GemmArgs g1{x, lda, m.w0, m.b0, t0, 768, rows, 768, 768, m.k_in, BG_F32, BG_ACT_NONE, nullptr, 0, 1};
+        GemmArgs g1 = linear(x, lda, m.w0, m.b0, t0, 768, rows, 768, 768, m.k_in, BG_F32);
         g1.gemv_ok = (&m == &c.w->time_embed);                    // one row per distinct timestep
-        g1.m_dev = m_dev; g1.rows_hint = hint;
+        if (vl) token_rows(c, g1, /*launch_plan=*/false);
         rc = gemm(g1, m.w0_dtype, c.s);
         if (rc) return rc;
-        rc = layernorm768(t0, m.ln_g, m.ln_b, c.H, c.dtype, rows, 1e-5f, /*silu=*/1, c.s, m_dev, hint);
+        rc = layernorm768(t0, m.ln_g, m.ln_b, c.H, c.dtype, rows, 1e-5f, /*silu=*/1, c.s, vl ? c.m_dev : nullptr, vl ? c.rows_hint : 0.0);
         if (rc) return rc;
     }
-    GemmArgs g2{c.H, 768, m.w3, m.b3, out, ldc, rows, m.n_out, m.n_out_pad, 768, BG_F32, BG_ACT_NONE, add, ld_add,
-                add ? add_div : 1};
-    g2.add2 = add2; g2.ld_add2 = ld_add2; g2.add2_div = add2 ? add2_div : 1;
-    g2.m_dev = m_dev; g2.rows_hint = hint;
-    if (vl && (map_add || map_add2 || scatter)) {
-        g2.row_map = c.src_row; g2.map_add = map_add; g2.map_add2 = map_add2; g2.map_out = scatter;
-    }
-    if (to_stream && c.fold) {
-        g2.out = c.XH; g2.out_dtype = c.dtype; g2.out_lo = c.XL; g2.stats_out = c.stats;
-        if (add == c.X) {                                         // accumulate into the stream
-            g2.add = nullptr; g2.ld_add = 0; g2.add_div = 1;
-            g2.res_hi = c.XH; g2.res_lo = c.XL; g2.ld_res = 768;
+    GemmArgs g2 = linear(c.H, 768, m.w3, m.b3, out, ldc, rows, m.n_out, m.n_out_pad, 768, BG_F32);
+    add_rows(g2, add.rows, add.ld, add.div);
+    add2_rows(g2, add2.rows, add2.ld, add2.div);
+    if (vl) token_rows(c, g2, /*launch_plan=*/false);
+    if (vl && (opt & (MAP_ADD | MAP_ADD2 | SCATTER))) map_rows(g2, c.src_row, opt & MAP_ADD, opt & MAP_ADD2, opt & SCATTER);
+    if ((opt & TO_STREAM) && c.fold) {
+        g2.out = c.XH; g2.out_dtype = c.dtype;
+        split_out(g2, c.XL, c.stats);
+        if (add.rows == c.X) {                                    // accumulate into the stream
+            add_rows(g2, nullptr, 0, 1);
+            split_residual_in(g2, c.XH, c.XL, 768);
         }
     }
     return gemm(g2, c.dtype, c.s);
 }
 
-// concurrent: sibling sample groups of the same call are in flight on forked streams (tells the GEMM launcher that a partial
-// round of tiles will be filled by the other group: bg_common.h p256_rows)
-static int run(const bg_denoiser_weights* w, const bg_denoiser_inputs* in, float* eps_out, void* workspace,
-               size_t ws_bytes, hipStream_t s, bool concurrent = false) {
+// One pre-LN encoder layer on the fp32 residual stream c.X, in place: LayerNorm kernels + unfolded weights (fp32 mode, and 16-bit
+// weights without the fold's column sums).  bg_encoder_layer_fwd is this routine with no variable-length context.
+static int encoder_layer_unfolded(const Ctx& c, const bg_layer_weights& L) {
+    int rc;
+    const int M = c.M;
+    if ((rc = layernorm768(c.X, L.ln1_g, L.ln1_b, c.H, c.dtype, M, 1e-5f, /*silu=*/0, c.s, c.m_dev, c.rows_hint))) return rc;
+    GemmArgs qkv = linear(c.H, 768, L.w_qkv, L.b_qkv, c.R, 2304, M, 2304, 2304, 768, c.dtype);
+    token_rows(c, qkv);
+    if ((rc = gemm(qkv, c.dtype, c.s))) return rc;
+    if ((rc = attention(c.R, c.key_pad, c.H, c.B, c.N, c.dtype, c.s, c.offsets, c.pairs_hint, c.rows_hint))) return rc;
+    GemmArgs op = linear(c.H, 768, L.w_o, L.b_o, c.X, 768, M, 768, 768, 768, BG_F32);
+    add_rows(op, c.X, 768, 1);
+    token_rows(c, op);
+    if ((rc = gemm(op, c.dtype, c.s))) return rc;
+    if ((rc = layernorm768(c.X, L.ln2_g, L.ln2_b, c.H, c.dtype, M, 1e-5f, /*silu=*/0, c.s, c.m_dev, c.rows_hint))) return rc;
+    GemmArgs f1 = linear(c.H, 768, L.w_1, L.b_1, c.R, 1024, M, 1024, 1024, 768, c.dtype, BG_ACT_RELU);
+    token_rows(c, f1);
+    if ((rc = gemm(f1, c.dtype, c.s))) return rc;
+    GemmArgs f2 = linear(c.R, 1024, L.w_2, L.b_2, c.X, 768, M, 768, 768, 1024, BG_F32);
+    add_rows(f2, c.X, 768, 1);
+    token_rows(c, f2);
+    return gemm(f2, c.dtype, c.s);
+}
+
+// The same layer on the split stream x = XH + XL (16-bit modes).  LN1 / LN2 are folded: QKV and FFN1 read the raw 16-bit rows XH
+// and normalise in their epilogue; out-proj and FFN2 add the split residual in place and leave the next fold's row statistics.
+static int encoder_layer_folded(const Ctx& c, const bg_layer_weights& L) {
+    int rc;
+    const int M = c.M;
+    if (c.paired) {
+        // ragged batch, slot-packed: one or two whole samples per 64-row slot (qkv_attn.hip, PAIR)
+        if ((rc = qkv_attention_paired(c.XH, L.w_qkv, L.b_qkv, L.qkv_colsum, c.stats, c.H, nullptr, c.m_dev, c.slot_desc,
+                                       c.B < (M + 63) / 64 ? c.B : (M + 63) / 64, M, c.dtype,
+                                       1e-5f, c.s, c.rows_hint, c.pairs_hint))) return rc;
+    } else if (c.fused_qkv) {
+        // short, equally long sequences (SurfPosNet; SurfZNet executed densely): q|k|v never leave the CU (qkv_attn.hip; bit-identical)
+        if ((rc = qkv_attention(c.XH, L.w_qkv, L.b_qkv, L.qkv_colsum, c.stats, c.H, c.key_pad, c.B, c.N, c.dtype, 1e-5f, c.s))) return rc;
+    } else {
+        GemmArgs qkv = linear(c.XH, 768, L.w_qkv, L.b_qkv, c.R, 2304, M, 2304, 2304, 768, c.dtype);
+        ln_fold_in(qkv, c.stats, L.qkv_colsum);
+        token_rows(c, qkv);
+        if ((rc = gemm(qkv, c.dtype, c.s))) return rc;
+        if ((rc = attention(c.R, c.key_pad, c.H, c.B, c.N, c.dtype, c.s, c.offsets, c.pairs_hint, c.rows_hint))) return rc;
+    }
+    GemmArgs op = linear(c.H, 768, L.w_o, L.b_o, c.XH, 768, M, 768, 768, 768, c.dtype);
+    split_out(op, c.XL, c.stats);
+    split_residual_in(op, c.XH, c.XL, 768);
+    token_rows(c, op);
+    if ((rc = gemm(op, c.dtype, c.s))) return rc;
+    if (L.w_1f && L.w_2f && g_tune[TUNE_FFN_FUSED] != 1) {
+        // FFN1 + ReLU + FFN2 + residual as one launch: the [M, 1024] hidden tensor stays in the CU's LDS (ffn_fused.hip; bit-identical)
+        FfnArgs ff{c.XH, c.XL, c.stats, L.w_1f, L.b_1, L.w1_colsum, L.w_2f, L.b_2, M, M, c.m_dev, 1e-5f};      // (statistics stride = the launch's row bound, as the GEMMs')
+        BG_REQUIRE(ffn_fused_eligible(ff, c.dtype), BG_E_ARG, "bg_denoiser_fwd: w_1f / w_2f given, but the fused FFN launch does not apply");
+        return ffn_fused(ff, c.dtype, c.s, c.rows_hint);
+    }
+    GemmArgs f1 = linear(c.XH, 768, L.w_1, L.b_1, c.R, 1024, M, 1024, 1024, 768, c.dtype, BG_ACT_RELU);
+    ln_fold_in(f1, c.stats, L.w1_colsum);
+    token_rows(c, f1);
+    if ((rc = gemm(f1, c.dtype, c.s))) return rc;
+    GemmArgs f2 = linear(c.R, 1024, L.w_2, L.b_2, c.XH, 768, M, 768, 768, 1024, c.dtype);
+    split_out(f2, c.XL, c.stats);
+    split_residual_in(f2, c.XH, c.XL, 768);
+    token_rows(c, f2);
+    return gemm(f2, c.dtype, c.s);
+}
+
+// ---- the stages of one whole-net forward, in the order run() calls them ---------------------------------------------------
+
+static int check_args(const bg_denoiser_weights* w, const bg_denoiser_inputs* in, const float* eps_out, const void* workspace) {
     const int net = w->net, B = in->B, S = in->S, E = (net >= BG_EDGEPOS) ? in->E : 1;
     BG_REQUIRE(net >= BG_SURFPOS && net <= BG_EDGEZ, BG_E_ARG, "bg_denoiser_fwd: bad net id %d", net);
     BG_REQUIRE(w->dtype == BG_BF16 || w->dtype == BG_F16 || w->dtype == BG_F32, BG_E_DTYPE, "bg_denoiser_fwd: compute dtype %d", w->dtype);
@@ -191,267 +223,193 @@ static int run(const bg_denoiser_weights* w, const bg_denoiser_inputs* in, float
     if (net >= BG_EDGEPOS) BG_REQUIRE(in->surf_z, BG_E_ARG, "bg_denoiser_fwd: surf_z missing");
     if (net == BG_EDGEZ) BG_REQUIRE(in->edge_pos, BG_E_ARG, "bg_denoiser_fwd: edge_pos missing");
     BG_REQUIRE(((uintptr_t)workspace & 255) == 0, BG_E_ALIGN, "bg_denoiser_fwd: workspace must be 256-byte aligned");
+    return 0;
+}
 
-    Ctx c;
-    c.w = w; c.s = s; c.dtype = w->dtype;
+// the call's shape, its execution mode (variable-length / slot-packed / LayerNorm fold) and the workspace regions
+static int bind_workspace(Ctx& c, const bg_denoiser_weights* w, const bg_denoiser_inputs* in, void* workspace, size_t ws_bytes) {
+    const int net = w->net, B = in->B, S = in->S, E = (net >= BG_EDGEPOS) ? in->E : 1;
+    c.w = w; c.in = in; c.dtype = w->dtype;
+    c.net = net; c.B = B; c.E = E; c.N = S * E;
     c.p = plan(net, B, S, E, w->dtype);
     BG_REQUIRE(ws_bytes >= c.p.total, BG_E_WORKSPACE, "bg_denoiser_fwd: workspace %zu < %zu bytes", ws_bytes, c.p.total);
     c.ws = reinterpret_cast<unsigned char*>(workspace);
     c.X = reinterpret_cast<float*>(c.ws + c.p.off_x);
     c.H = c.ws + c.p.off_h;
     c.R = c.ws + c.p.off_r;
-    const int Mpad = c.p.M, F = c.p.F, N = S * E, nt = in->n_timesteps;
-    // ---- variable-length execution: compact the valid tokens (row count stays on the device) ----------------------
-    const bool varlen = in->varlen != 0 && in->mask != nullptr && net != BG_SURFPOS;
+    c.cvec = reinterpret_cast<float*>(c.ws + c.p.off_small) + (size_t)4 * B * 768;
+    // variable-length execution: the valid tokens are compacted (row count stays on the device)
+    c.varlen = in->varlen != 0 && in->mask != nullptr && net != BG_SURFPOS;
     // ragged batches of short sequences: slot-packed rows + the fused QKV / attention launch (bg_tune key 13 = 1: dense packing +
     // GEMM + attention, the bit-equality baseline)
-    const bool paired = varlen && slot_packing_applies(net, B, S, E, w->dtype) && w->n_layer > 0 && w->layers[0].qkv_colsum != nullptr &&
-                        g_tune[TUNE_QKV_ATTN] != 1;
-    const int M = paired ? c.p.Mrow : Mpad;                       // row bound of every token-wise launch
+    c.paired = c.varlen && slot_packing_applies(net, B, S, E, w->dtype) && w->n_layer > 0 && w->layers[0].qkv_colsum != nullptr &&
+               g_tune[TUNE_QKV_ATTN] != 1;
+    c.M = c.paired ? c.p.Mrow : c.p.M;
     c.fold = w->dtype != BG_F32 && w->n_layer > 0 && w->layers[0].qkv_colsum != nullptr;
     if (c.fold) {
         for (int li = 0; li < w->n_layer; ++li)
             BG_REQUIRE(w->layers[li].qkv_colsum && w->layers[li].w1_colsum, BG_E_ARG,
                        "bg_denoiser_fwd: layer %d lacks the LayerNorm-fold column sums", li);
         c.XH = c.X;
-        c.XL = reinterpret_cast<unsigned char*>(c.X) + (size_t)M * 768 * 2;
+        c.XL = reinterpret_cast<unsigned char*>(c.X) + (size_t)c.M * 768 * 2;
         c.stats = reinterpret_cast<float*>(c.ws + c.p.off_stats);
     }
-    c.N_tok = N;
-    c.concurrent = concurrent ? 1 : 0;
-    if (varlen) {
-        int* offs = reinterpret_cast<int*>(c.ws + c.p.off_rows);
-        int* srow = reinterpret_cast<int*>(c.ws + c.p.off_rows + align_up((size_t)(B + 2 + P256_RULE_ENTRIES) * 4));
-        const int n_mask = (net == BG_EDGEPOS) ? S : N, rep = (net == BG_EDGEPOS) ? E : 1;
-        int rcc;
-        if (paired) {
-            int* sd = reinterpret_cast<int*>(c.ws + c.p.off_slots);
-            rcc = compact_rows_paired(in->mask, B, n_mask, offs, srow, sd, sd + 2 * B, sd + 3 * B, s, offs + B + 2);
-            c.slot_desc = sd;
-        } else {
-            rcc = compact_rows(in->mask, B, n_mask, rep, offs, srow, s, offs + B + 2);
-        }
-        if (rcc) return rcc;
-        c.offsets = offs; c.m_dev = offs + B; c.src_row = srow; c.rule = offs + B + 2;
-        c.rows_hint = in->rows_hint > 0 ? in->rows_hint : 0.0;
-        c.pairs_hint = in->pairs_hint > 0 ? in->pairs_hint : 0.0;
-        c.rows_plan = in->rows_plan[0] > 0 ? in->rows_plan[0] : 0.0;
-        // padded positions of the result are defined as 0 (the valid rows are scattered over this)
-        const hipError_t he = hipMemsetAsync(eps_out, 0, (size_t)Mpad * w->fc_out.n_out * sizeof(float), s);
-        BG_REQUIRE(he == hipSuccess, (int)he, "bg_denoiser_fwd: hipMemsetAsync failed: %s", hipGetErrorString(he));
-    }
-    float* small = reinterpret_cast<float*>(c.ws + c.p.off_small);
-    float* sc = small;                         // [nt,768] sincos
-    float* temb = small + (size_t)3 * B * 768; // [nt,768]
-    float* cvec = small + (size_t)4 * B * 768; // [B,768] = time (+ class) embedding per sample
+    return 0;
+}
+
+// variable-length execution: compact the valid tokens, zero the padded positions of the result
+static int setup_varlen(Ctx& c, float* eps_out) {
+    const bg_denoiser_inputs* in = c.in;
+    const int B = c.B;
+    int* offs = reinterpret_cast<int*>(c.ws + c.p.off_rows);
+    int* srow = reinterpret_cast<int*>(c.ws + c.p.off_rows + align_up((size_t)(B + 2 + P256_RULE_ENTRIES) * 4));
+    const int n_mask = (c.net == BG_EDGEPOS) ? in->S : c.N, rep = (c.net == BG_EDGEPOS) ? c.E : 1;
     int rc;
-
-    // ---- time (+class) embedding -> one vector per sample --------------------------------------------------
-    if (w->time_table != nullptr && w->time_table_rows > 0) {
-        // the time-embedding MLP is a function of the weights and the timestep only: looked up in the table the caller precomputed
-        if ((rc = cond_vector_table(w->time_table, w->time_table_rows, in->timesteps, nt, w->class_embed, in->class_label, cvec, B, s))) return rc;
+    if (c.paired) {
+        int* sd = reinterpret_cast<int*>(c.ws + c.p.off_slots);
+        rc = compact_rows_paired(in->mask, B, n_mask, offs, srow, sd, sd + 2 * B, sd + 3 * B, c.s, offs + B + 2);
+        c.slot_desc = sd;
     } else {
-        if ((rc = sincos_embed(in->timesteps, nt, sc, s))) return rc;
-        if ((rc = embed_mlp(c, w->time_embed, sc, 768, nt, temb, 768, nullptr, 0, 1, nullptr, 0, 1))) return rc;
-        if ((rc = cond_vector(temb, nt, w->class_embed, in->class_label, cvec, B, s))) return rc;
+        rc = compact_rows(in->mask, B, n_mask, rep, offs, srow, c.s, offs + B + 2);
     }
+    if (rc) return rc;
+    c.offsets = offs; c.m_dev = offs + B; c.src_row = srow; c.rule = offs + B + 2;
+    c.rows_hint = in->rows_hint > 0 ? in->rows_hint : 0.0;
+    c.pairs_hint = in->pairs_hint > 0 ? in->pairs_hint : 0.0;
+    c.rows_plan = in->rows_plan[0] > 0 ? in->rows_plan[0] : 0.0;
+    // padded positions of the result are defined as 0 (the valid rows are scattered over this)
+    const hipError_t he = hipMemsetAsync(eps_out, 0, (size_t)c.p.M * c.w->fc_out.n_out * sizeof(float), c.s);
+    BG_REQUIRE(he == hipSuccess, (int)he, "bg_denoiser_fwd: hipMemsetAsync failed: %s", hipGetErrorString(he));
+    return 0;
+}
 
-    // ---- token embeddings -> X [M,768] fp32 ----------------------------------------------------------------
+// time (+ class) embedding -> one vector per sample, c.cvec
+static int cond_vectors(Ctx& c) {
+    const bg_denoiser_weights* w = c.w;
+    const bg_denoiser_inputs* in = c.in;
+    const int nt = in->n_timesteps;
+    // the time-embedding MLP is a function of the weights and the timestep only: looked up in the table the caller precomputed
+    if (w->time_table != nullptr && w->time_table_rows > 0)
+        return cond_vector_table(w->time_table, w->time_table_rows, in->timesteps, nt, w->class_embed, in->class_label, c.cvec, c.B, c.s);
+    float* small = reinterpret_cast<float*>(c.ws + c.p.off_small);
+    float* sc = small;                           // [nt,768] sincos
+    float* temb = small + (size_t)3 * c.B * 768; // [nt,768]
+    int rc;
+    if ((rc = sincos_embed(in->timesteps, nt, sc, c.s))) return rc;
+    if ((rc = embed_mlp(c, w->time_embed, sc, 768, nt, temb, 768))) return rc;
+    return cond_vector(temb, nt, w->class_embed, in->class_label, c.cvec, c.B, c.s);
+}
+
+// token embeddings -> the stream X [M,768]
+static int token_embeds(Ctx& c) {
+    const bg_denoiser_weights* w = c.w;
+    const bg_denoiser_inputs* in = c.in;
+    const int net = c.net, M = c.M, N = c.N, E = c.E, F = c.p.F;
+    int rc;
     // step-invariant part (per face): SurfZ: p_embed(surfPos); Edge nets: surfp_embed(surfPos)+surfz_embed(surfZ)
     float* fcond = nullptr;
     // SurfZNet, variable-length, no conditioning cache: p_embed(surfPos) is computed on the compact rows (the cache, when
     // the caller provides one, stays in the padded per-face layout so that it does not depend on the mask)
-    const bool fcond_compact = varlen && net == BG_SURFZ && in->cond_cache == nullptr;
+    const bool fcond_compact = c.varlen && net == BG_SURFZ && in->cond_cache == nullptr;
     if (net != BG_SURFPOS) {
         fcond = in->cond_cache ? in->cond_cache : reinterpret_cast<float*>(c.ws + c.p.off_f);
         if (!(in->cond_cache && in->cond_cache_valid)) {
             if (net == BG_SURFZ && fcond_compact) {
                 // faces == tokens: without a cache to fill, only the valid faces need their conditioning embed
-                if ((rc = embed_mlp(c, w->embed[1], in->surf_pos, 6, paired ? M : F, fcond, 768, nullptr, 0, 1, nullptr, 0, 1, false, true, true))) return rc;
+                if ((rc = embed_mlp(c, w->embed[1], in->surf_pos, 6, c.paired ? M : F, fcond, 768, {}, {}, TOK | GATHER))) return rc;
             } else if (net == BG_SURFZ) {
-                if ((rc = embed_mlp(c, w->embed[1], in->surf_pos, 6, F, fcond, 768, nullptr, 0, 1, nullptr, 0, 1))) return rc;
+                if ((rc = embed_mlp(c, w->embed[1], in->surf_pos, 6, F, fcond, 768))) return rc;
             } else {
-                if ((rc = embed_mlp(c, w->embed[0], in->surf_pos, 6, F, fcond, 768, nullptr, 0, 1, nullptr, 0, 1))) return rc;
-                if ((rc = embed_mlp(c, w->embed[1], in->surf_z, 48, F, fcond, 768, fcond, 768, 1, nullptr, 0, 1))) return rc;
+                if ((rc = embed_mlp(c, w->embed[0], in->surf_pos, 6, F, fcond, 768))) return rc;
+                if ((rc = embed_mlp(c, w->embed[1], in->surf_z, 48, F, fcond, 768, Addend{fcond, 768, 1}))) return rc;
             }
         }
     }
+    // (variable-length: rows are the compact tokens; x is gathered, cvec [B] and the per-face conditioning
+    //  fcond [B*S] -- kept in the padded layout, so the conditioning cache is unaffected -- are looked up through the
+    //  row map: sample = token / N, face = token / E)
+    const Addend per_sample{c.cvec, 768, N}, stream{c.X, 768, 1};
+    const unsigned tokens = TO_STREAM | TOK | GATHER;
     switch (net) {
         case BG_SURFPOS:   // tokens = p_embed(x) + c
-            rc = embed_mlp(c, w->embed[0], in->x, 6, M, c.X, 768, cvec, 768, N, nullptr, 0, 1, true);
-            break;
-        // (variable-length: rows are the compact tokens; x is gathered, cvec [B] and the per-face conditioning
-        //  fcond [B*S] -- kept in the padded layout, so the conditioning cache is unaffected -- are looked up through the
-        //  row map: sample = token / N, face = token / E)
+            return embed_mlp(c, w->embed[0], in->x, 6, M, c.X, 768, per_sample, {}, TO_STREAM);
         case BG_SURFZ:     // tokens = z_embed(x) + p_embed(surfPos) + c
-            rc = embed_mlp(c, w->embed[0], in->x, 48, M, c.X, 768, cvec, 768, N, fcond, 768, 1, true, true, true, true, !fcond_compact);
-            break;
+            return embed_mlp(c, w->embed[0], in->x, 48, M, c.X, 768, per_sample, Addend{fcond, 768, 1},
+                             tokens | MAP_ADD | (fcond_compact ? 0 : MAP_ADD2));
         case BG_EDGEPOS:   // tokens = edgep_embed(x) + surf[m/E] + c
-            rc = embed_mlp(c, w->embed[2], in->x, 6, M, c.X, 768, cvec, 768, N, fcond, 768, E, true, true, true, true, true);
-            break;
+            return embed_mlp(c, w->embed[2], in->x, 6, M, c.X, 768, per_sample, Addend{fcond, 768, E}, tokens | MAP_ADD | MAP_ADD2);
         default:           // EdgeZ: edgez_embed(x[:, :12]) + vertp_fc(x[:, 12:]) + edgep_embed(edgePos) + surf[m/E] + c
-            rc = embed_mlp(c, w->embed[3], in->x, 18, M, c.X, 768, cvec, 768, N, fcond, 768, E, true, true, true, true, true);
-            if (!rc) rc = embed_mlp(c, w->embed[4], in->x + 12, 18, M, c.X, 768, c.X, 768, 1, nullptr, 0, 1, true, true, true);
-            if (!rc) rc = embed_mlp(c, w->embed[2], in->edge_pos, 6, M, c.X, 768, c.X, 768, 1, nullptr, 0, 1, true, true, true);
-            break;
+            if ((rc = embed_mlp(c, w->embed[3], in->x, 18, M, c.X, 768, per_sample, Addend{fcond, 768, E}, tokens | MAP_ADD | MAP_ADD2))) return rc;
+            if ((rc = embed_mlp(c, w->embed[4], in->x + 12, 18, M, c.X, 768, stream, {}, tokens))) return rc;
+            return embed_mlp(c, w->embed[2], in->edge_pos, 6, M, c.X, 768, stream, {}, tokens);
     }
-    if (rc) return rc;
+}
 
-    // ---- key-padding mask [B,N] ----------------------------------------------------------------------------
-    const uint8_t* key_pad = in->mask;
-    if (varlen) key_pad = nullptr;                                // every compact row is a valid key
-    if (net == BG_EDGEPOS && in->mask && !varlen) {
+// key-padding mask [B,N] + the pre-LN encoder layers
+static int encoder_layers(Ctx& c) {
+    const bg_denoiser_weights* w = c.w;
+    int rc;
+    c.key_pad = c.varlen ? nullptr : c.in->mask;                  // (variable-length: every compact row is a valid key)
+    if (c.net == BG_EDGEPOS && c.in->mask && !c.varlen) {
         uint8_t* mexp = c.ws + c.p.off_mask;
-        const size_t n = (size_t)M;
+        const size_t n = (size_t)c.M;
         const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-        hipLaunchKernelGGL(expand_mask_kernel, dim3(grid), dim3(256), 0, s, in->mask, mexp, n, E);
+        hipLaunchKernelGGL(expand_mask_kernel, dim3(grid), dim3(256), 0, c.s, c.in->mask, mexp, n, c.E);
         if ((rc = launch_status("expand_mask"))) return rc;
-        key_pad = mexp;
+        c.key_pad = mexp;
     }
+    BG_REQUIRE(!c.paired || c.fold, BG_E_ARG, "bg_denoiser_fwd: slot-packed execution needs the LayerNorm-fold operands");
+    c.fused_qkv = c.fold && !c.varlen && g_tune[TUNE_QKV_ATTN] != 1 &&
+                  qkv_attn_eligible(c.B, c.N, c.dtype, c.stats, w->layers[0].qkv_colsum, w->layers[0].b_qkv) &&
+                  (g_tune[TUNE_QKV_ATTN] == 2 || qkv_attn_worthwhile(c.B, c.N));
+    for (int li = 0; li < w->n_layer; ++li)
+        if ((rc = c.fold ? encoder_layer_folded(c, w->layers[li]) : encoder_layer_unfolded(c, w->layers[li]))) return rc;
+    return 0;
+}
 
-    // ---- 12 pre-LN encoder layers ---------------------------------------------------------------------------
-    BG_REQUIRE(!paired || c.fold, BG_E_ARG, "bg_denoiser_fwd: slot-packed execution needs the LayerNorm-fold operands");
-    const bool fused_qkv = c.fold && !varlen && g_tune[TUNE_QKV_ATTN] != 1 &&
-                           qkv_attn_eligible(B, N, c.dtype, c.stats, w->layers[0].qkv_colsum, w->layers[0].b_qkv) &&
-                           (g_tune[TUNE_QKV_ATTN] == 2 || qkv_attn_worthwhile(B, N));
-    for (int li = 0; c.fold && li < w->n_layer; ++li) {
-        // x = XH + XL.  LN1 / LN2 are folded: QKV and FFN1 read the raw 16-bit rows XH and normalise in their epilogue.
-        const bg_layer_weights& L = w->layers[li];
-        GemmArgs qkv{c.XH, 768, L.w_qkv, L.b_qkv, c.R, 2304, M, 2304, 2304, 768, c.dtype, BG_ACT_NONE, nullptr, 0, 1};
-        qkv.stats_in = c.stats; qkv.colsum = L.qkv_colsum;
-        qkv.m_dev = c.m_dev; qkv.rule_table = c.rule; qkv.rows_hint = c.rows_hint; qkv.rows_plan = c.rows_plan; qkv.concurrent = c.concurrent;
-        if (paired) {
-            // ragged batch, slot-packed: one or two whole samples per 64-row slot (qkv_attn.hip, PAIR)
-            if ((rc = qkv_attention_paired(c.XH, L.w_qkv, L.b_qkv, L.qkv_colsum, c.stats, c.H, nullptr, c.m_dev, c.slot_desc,
-                                           B < (M + 63) / 64 ? B : (M + 63) / 64, M, c.dtype,
-                                           1e-5f, s, c.rows_hint, c.pairs_hint))) return rc;
-        } else if (fused_qkv) {
-            // short, equally long sequences (SurfPosNet; SurfZNet executed densely): q|k|v never leave the CU (qkv_attn.hip; bit-identical)
-            if ((rc = qkv_attention(c.XH, L.w_qkv, L.b_qkv, L.qkv_colsum, c.stats, c.H, key_pad, B, N, c.dtype, 1e-5f, s))) return rc;
-        } else {
-            if ((rc = gemm(qkv, c.dtype, s))) return rc;
-            if ((rc = attention(c.R, key_pad, c.H, B, N, c.dtype, s, c.offsets, c.pairs_hint, c.rows_hint))) return rc;
-        }
-        GemmArgs op{c.H, 768, L.w_o, L.b_o, c.XH, 768, M, 768, 768, 768, c.dtype, BG_ACT_NONE, nullptr, 0, 1};
-        op.out_lo = c.XL; op.res_hi = c.XH; op.res_lo = c.XL; op.ld_res = 768; op.stats_out = c.stats;
-        op.m_dev = c.m_dev; op.rule_table = c.rule; op.rows_hint = c.rows_hint; op.rows_plan = c.rows_plan; op.concurrent = c.concurrent;
-        if ((rc = gemm(op, c.dtype, s))) return rc;
-        if (L.w_1f && L.w_2f && g_tune[TUNE_FFN_FUSED] != 1) {
-            // FFN1 + ReLU + FFN2 + residual as one launch: the [M, 1024] hidden tensor stays in the CU's LDS (ffn_fused.hip; bit-identical)
-            FfnArgs ff{c.XH, c.XL, c.stats, L.w_1f, L.b_1, L.w1_colsum, L.w_2f, L.b_2, M, M, c.m_dev, 1e-5f};      // (statistics stride = the launch's row bound, as the GEMMs')
-            BG_REQUIRE(ffn_fused_eligible(ff, c.dtype), BG_E_ARG, "bg_denoiser_fwd: w_1f / w_2f given, but the fused FFN launch does not apply");
-            if ((rc = ffn_fused(ff, c.dtype, s, c.rows_hint))) return rc;
-            continue;
-        }
-        GemmArgs f1{c.XH, 768, L.w_1, L.b_1, c.R, 1024, M, 1024, 1024, 768, c.dtype, BG_ACT_RELU, nullptr, 0, 1};
-        f1.stats_in = c.stats; f1.colsum = L.w1_colsum;
-        f1.m_dev = c.m_dev; f1.rule_table = c.rule; f1.rows_hint = c.rows_hint; f1.rows_plan = c.rows_plan; f1.concurrent = c.concurrent;
-        if ((rc = gemm(f1, c.dtype, s))) return rc;
-        GemmArgs f2{c.R, 1024, L.w_2, L.b_2, c.XH, 768, M, 768, 768, 1024, c.dtype, BG_ACT_NONE, nullptr, 0, 1};
-        f2.out_lo = c.XL; f2.res_hi = c.XH; f2.res_lo = c.XL; f2.ld_res = 768; f2.stats_out = c.stats;
-        f2.m_dev = c.m_dev; f2.rule_table = c.rule; f2.rows_hint = c.rows_hint; f2.rows_plan = c.rows_plan; f2.concurrent = c.concurrent;
-        if ((rc = gemm(f2, c.dtype, s))) return rc;
-    }
-    for (int li = 0; !c.fold && li < w->n_layer; ++li) {
-        const bg_layer_weights& L = w->layers[li];
-        auto vl = [&](GemmArgs& g) { g.m_dev = c.m_dev; g.rule_table = c.rule; g.rows_hint = c.rows_hint; g.rows_plan = c.rows_plan; g.concurrent = c.concurrent; };
-        if ((rc = layernorm768(c.X, L.ln1_g, L.ln1_b, c.H, c.dtype, M, 1e-5f, 0, s, c.m_dev, c.rows_hint))) return rc;
-        GemmArgs qkv{c.H, 768, L.w_qkv, L.b_qkv, c.R, 2304, M, 2304, 2304, 768, c.dtype, BG_ACT_NONE, nullptr, 0, 1};
-        vl(qkv);
-        if ((rc = gemm(qkv, c.dtype, s))) return rc;
-        if ((rc = attention(c.R, key_pad, c.H, B, N, c.dtype, s, c.offsets, c.pairs_hint, c.rows_hint))) return rc;
-        GemmArgs op{c.H, 768, L.w_o, L.b_o, c.X, 768, M, 768, 768, 768, BG_F32, BG_ACT_NONE, c.X, 768, 1};
-        vl(op);
-        if ((rc = gemm(op, c.dtype, s))) return rc;
-        if ((rc = layernorm768(c.X, L.ln2_g, L.ln2_b, c.H, c.dtype, M, 1e-5f, 0, s, c.m_dev, c.rows_hint))) return rc;
-        GemmArgs f1{c.H, 768, L.w_1, L.b_1, c.R, 1024, M, 1024, 1024, 768, c.dtype, BG_ACT_RELU, nullptr, 0, 1};
-        vl(f1);
-        if ((rc = gemm(f1, c.dtype, s))) return rc;
-        GemmArgs f2{c.R, 1024, L.w_2, L.b_2, c.X, 768, M, 768, 768, 1024, BG_F32, BG_ACT_NONE, c.X, 768, 1};
-        vl(f2);
-        if ((rc = gemm(f2, c.dtype, s))) return rc;
-    }
-
-    // ---- final LayerNorm + fc_out ---------------------------------------------------------------------------
-    const bg_mlp_weights& mo = w->fc_out;
+// final LayerNorm + fc_out -> eps_out (variable-length: the compact result rows are scattered into the zero-filled padded eps_out)
+static int output_tail(Ctx& c, float* eps_out) {
+    const bg_mlp_weights& mo = c.w->fc_out;
+    const int M = c.M;
+    int rc;
     if (mo.w0_colsum != nullptr) {
         BG_REQUIRE(c.fold && mo.w0_dtype == c.dtype && ln_silu_out_supported(mo.n_out, mo.n_out_pad), BG_E_ARG,
                    "bg_denoiser_fwd: fc_out carries the folded final LayerNorm (w0_colsum): needs the 16-bit LayerNorm-fold layers and n_out <= 48");
         // 16-bit modes: the final LayerNorm is folded into fc_out.0 (the epilogue of QKV / FFN1: raw XH rows in, the statistics the
         // last FFN2 left behind), and LayerNorm + SiLU + Linear(768, n_out) are one launch (out_tail.hip) -- two launches, and the
         // [M, 768] intermediate crosses HBM once, in 16 bits
-        GemmArgs g0{c.XH, 768, mo.w0, mo.b0, c.H, 768, M, 768, 768, 768, c.dtype, BG_ACT_NONE, nullptr, 0, 1};
-        g0.stats_in = c.stats; g0.colsum = mo.w0_colsum;
-        g0.m_dev = c.m_dev; g0.rule_table = c.rule; g0.rows_hint = c.rows_hint; g0.rows_plan = c.rows_plan; g0.concurrent = c.concurrent;
-        if ((rc = gemm(g0, c.dtype, s))) return rc;
-        // (variable-length: the compact result rows are scattered into the zero-filled padded eps_out)
-        return ln_silu_out(c.H, mo.ln_g, mo.ln_b, mo.w3, mo.b3, eps_out, mo.n_out, mo.n_out_pad, M, c.dtype, 1e-5f, s, c.m_dev,
-                           varlen ? c.src_row : nullptr, c.rows_hint);
+        GemmArgs g0 = linear(c.XH, 768, mo.w0, mo.b0, c.H, 768, M, 768, 768, 768, c.dtype);
+        ln_fold_in(g0, c.stats, mo.w0_colsum);
+        token_rows(c, g0);
+        if ((rc = gemm(g0, c.dtype, c.s))) return rc;
+        return ln_silu_out(c.H, mo.ln_g, mo.ln_b, mo.w3, mo.b3, eps_out, mo.n_out, mo.n_out_pad, M, c.dtype, 1e-5f, c.s, c.m_dev,
+                           c.varlen ? c.src_row : nullptr, c.rows_hint);
     }
     // fc_out.0 reads the final-LN output from H and writes its fp32 result to R; the LN+SiLU then overwrites H.
-    {
-        void* hf = c.H;
-        if (c.fold) rc = layernorm768_split(c.XH, c.XL, w->lnf_g, w->lnf_b, hf, c.dtype, M, 1e-5f, s, c.m_dev, c.rows_hint);
-        else rc = layernorm768(c.X, w->lnf_g, w->lnf_b, hf, c.dtype, M, 1e-5f, 0, s, c.m_dev, c.rows_hint);
-        if (rc) return rc;
-        // (variable-length: the compact result rows are scattered into the zero-filled padded eps_out)
-        rc = embed_mlp(c, mo, hf, 768, M, eps_out, mo.n_out, nullptr, 0, 1, nullptr, 0, 1, false, true, false, false, false, true);
-    }
-    return rc;
+    if (c.fold) rc = layernorm768_split(c.XH, c.XL, c.w->lnf_g, c.w->lnf_b, c.H, c.dtype, M, 1e-5f, c.s, c.m_dev, c.rows_hint);
+    else rc = layernorm768(c.X, c.w->lnf_g, c.w->lnf_b, c.H, c.dtype, M, 1e-5f, /*silu=*/0, c.s, c.m_dev, c.rows_hint);
+    if (rc) return rc;
+    return embed_mlp(c, mo, c.H, 768, M, eps_out, mo.n_out, {}, {}, TOK | SCATTER);
+}
+
+// concurrent: sibling sample groups of the same call are in flight on forked streams (tells the GEMM launcher that a partial
+// round of tiles will be filled by the other group: bg_common.h p256_rows)
+static int run(const bg_denoiser_weights* w, const bg_denoiser_inputs* in, float* eps_out, void* workspace,
+               size_t ws_bytes, hipStream_t s, bool concurrent = false) {
+    int rc;
+    if ((rc = check_args(w, in, eps_out, workspace))) return rc;
+    Ctx c;
+    c.s = s;
+    c.concurrent = concurrent ? 1 : 0;
+    if ((rc = bind_workspace(c, w, in, workspace, ws_bytes))) return rc;
+    if (c.varlen && (rc = setup_varlen(c, eps_out))) return rc;
+    if ((rc = cond_vectors(c))) return rc;
+    if ((rc = token_embeds(c))) return rc;
+    if ((rc = encoder_layers(c))) return rc;
+    return output_tail(c, eps_out);
 }
 
 }  // namespace bg
-
-extern "C" int bg_profile_begin(int max_launches) {
-    using namespace bg;
-    BG_REQUIRE(max_launches > 0 && max_launches <= (1 << 20), BG_E_ARG, "bg_profile_begin: bad max_launches");
-    BG_REQUIRE(g_recs == nullptr, BG_E_ARG, "bg_profile_begin: already profiling");
-    g_recs = new ProfRec[max_launches];
-    for (int i = 0; i < max_launches; ++i) {
-        if (hipEventCreate(&g_recs[i].e0) != hipSuccess || hipEventCreate(&g_recs[i].e1) != hipSuccess) {
-            set_error("bg_profile_begin: hipEventCreate failed");
-            return BG_E_ARG;
-        }
-    }
-    g_cap = max_launches; g_n = 0; g_prof_on = true;
-    return 0;
-}
-
-extern "C" int bg_profile_end(bg_profile_row* rows, int max_rows) {
-    using namespace bg;
-    BG_REQUIRE(g_recs != nullptr, BG_E_ARG, "bg_profile_end: not profiling");
-    g_prof_on = false;
-    (void)hipDeviceSynchronize();            // measurement aid only -- never on the product path
-    bg_profile_row agg[PK_COUNT];
-    for (int k = 0; k < PK_COUNT; ++k) agg[k] = bg_profile_row{kProfNames[k], 0, 0.0, 0.0, 0.0};
-    for (int i = 0; i < g_n; ++i) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, g_recs[i].e0, g_recs[i].e1) != hipSuccess) continue;
-        bg_profile_row& a = agg[g_recs[i].kernel];
-        a.launches += 1; a.total_ms += ms; a.flops += g_recs[i].flops; a.bytes += g_recs[i].bytes;
-    }
-    for (int i = 0; i < g_cap; ++i) { (void)hipEventDestroy(g_recs[i].e0); (void)hipEventDestroy(g_recs[i].e1); }
-    delete[] g_recs;
-    g_recs = nullptr; g_cap = 0; g_n = 0;
-    int n = 0;
-    for (int k = 0; k < PK_COUNT && n < max_rows; ++k)
-        if (agg[k].launches > 0 && rows) rows[n++] = agg[k];
-    return n;
-}
-
-extern "C" int bg_tune_set(int key, int value) {
-    BG_REQUIRE(key >= 0 && key < bg::TUNE_COUNT, BG_E_ARG, "bg_tune_set: unknown key %d", key);
-    bg::g_tune[key] = value;
-    return 0;
-}
-
-extern "C" int bg_gemm_p256_rows(int rows, int n_cols, int split_residual, int concurrent) {
-    BG_REQUIRE(rows >= 0 && n_cols > 0 && (n_cols & 255) == 0, BG_E_ARG, "bg_gemm_p256_rows: rows >= 0 and n_cols a positive multiple of 256 expected");
-    return bg::p256_rows(rows, n_cols >> 8, split_residual != 0, concurrent != 0);
-}
-
-extern "C" int bg_abi_version(void) { return BG_ABI_VERSION; }
-extern "C" const char* bg_last_error(void) { return bg::g_err; }
 
 namespace bg {
 constexpr int MAX_SPLIT = 4;
@@ -598,7 +556,7 @@ extern "C" int bg_embed_mlp_fwd(const bg_mlp_weights* m, int dtype, const void* 
     c.X = nullptr;
     c.H = c.ws;
     c.R = c.ws + align_up((size_t)rows * 768 * ((dtype == BG_F32) ? 4 : 2));
-    return embed_mlp(c, *m, x, lda, rows, out, ldc, add, ld_add, add ? add_div : 1, nullptr, 0, 1);
+    return embed_mlp(c, *m, x, lda, rows, out, ldc, Addend{add, ld_add, add_div});
 }
 
 extern "C" size_t bg_encoder_layer_scratch_bytes(int B, int N, int dtype) {
@@ -606,6 +564,7 @@ extern "C" size_t bg_encoder_layer_scratch_bytes(int B, int N, int dtype) {
     const size_t es = (dtype == BG_F32) ? 4 : 2, M = (size_t)B * N;
     return bg::align_up(M * 768 * es) + bg::align_up(M * 2304 * es);
 }
+
 
 // One pre-LN encoder layer (nn.TransformerEncoderLayer(norm_first=True), network.py:1076-1078) on an fp32 residual
 // stream x [B*N, 768], in place -- the unfolded formulation: LayerNorm kernels + unfolded weights (qkv_colsum == NULL).
@@ -619,22 +578,11 @@ extern "C" int bg_encoder_layer_fwd(const bg_layer_weights* L, int dtype, float*
                "bg_encoder_layer_fwd: takes unfolded weights (the LayerNorm-folded layers run inside bg_denoiser_fwd)");
     BG_REQUIRE(scratch_bytes >= bg_encoder_layer_scratch_bytes(B, N, dtype), BG_E_WORKSPACE, "bg_encoder_layer_fwd: scratch too small");
     BG_REQUIRE(((uintptr_t)scratch & 255) == 0, BG_E_ALIGN, "bg_encoder_layer_fwd: scratch must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const int M = B * N;
-    unsigned char* ws = reinterpret_cast<unsigned char*>(scratch);
-    void* H = ws;
-    void* R = ws + align_up((size_t)M * 768 * ((dtype == BG_F32) ? 4 : 2));
-    int rc;
-    if ((rc = layernorm768(x, L->ln1_g, L->ln1_b, H, dtype, M, 1e-5f, 0, s))) return rc;
-    GemmArgs qkv{H, 768, L->w_qkv, L->b_qkv, R, 2304, M, 2304, 2304, 768, dtype, BG_ACT_NONE, nullptr, 0, 1};
-    if ((rc = gemm(qkv, dtype, s))) return rc;
-    if ((rc = attention(R, key_pad, H, B, N, dtype, s))) return rc;
-    GemmArgs op{H, 768, L->w_o, L->b_o, x, 768, M, 768, 768, 768, BG_F32, BG_ACT_NONE, x, 768, 1};
-    if ((rc = gemm(op, dtype, s))) return rc;
-    if ((rc = layernorm768(x, L->ln2_g, L->ln2_b, H, dtype, M, 1e-5f, 0, s))) return rc;
-    GemmArgs f1{H, 768, L->w_1, L->b_1, R, 1024, M, 1024, 1024, 768, dtype, BG_ACT_RELU, nullptr, 0, 1};
-    if ((rc = gemm(f1, dtype, s))) return rc;
-    GemmArgs f2{R, 1024, L->w_2, L->b_2, x, 768, M, 768, 768, 1024, BG_F32, BG_ACT_NONE, x, 768, 1};
-    return gemm(f2, dtype, s);
+    Ctx c;
+    c.w = nullptr; c.s = (hipStream_t)stream; c.dtype = dtype; c.ws = reinterpret_cast<unsigned char*>(scratch);
+    c.B = B; c.N = N; c.M = B * N; c.key_pad = key_pad;
+    c.X = x;
+    c.H = c.ws;
+    c.R = c.ws + align_up((size_t)c.M * 768 * ((dtype == BG_F32) ? 4 : 2));
+    return encoder_layer_unfolded(c, *L);
 }
-

@@ -853,20 +853,21 @@ static int launch16(const GemmArgs& g, hipStream_t s) {
     // 256 x 256 persistent kernel (gemm_p256.hip) on the row panels that fill complete rounds of tiles; a 128 x 128 kernel below
     // runs the remaining rows (bg_common.h: p256_rows).  With a device-side row count the split is only known on the device: both
     // kernels are launched and evaluate the same rule.  bg_tune key 10: 0 = hybrid, 1 = 256 kernel alone wherever eligible, 2 = never.
-    bool tail_only = false;
+    GemmArgs gt = g;                                              // what the 128 x 128 kernels below see
+    gt.hybrid = 0;
     if (g_tune[TUNE_P256_MODE] != 2 && p256_eligible(g)) {
-        double fl, by;
         const bool split = g.out_lo != nullptr;
-        if (g_tune[TUNE_P256_MODE] == 1) {
-            gemm_cost(g, rows_all, fl, by);
-            ProfScope prof(split ? PK_GEMM_P256_SPLIT : PK_GEMM_P256, fl, by, s);     // (booked apart: HBM-bound vs MFMA-bound launches)
-            GemmArgs h = g;
+        const int hmode = g.concurrent ? 2 : 1;
+        // the 256 x 256 kernel on h's rows, booked as `rows` rows under the key of its kind (apart: HBM-bound vs MFMA-bound launches),
+        // the phase groups of a split-residual launch staggered
+        auto p256 = [&](GemmArgs h, double rows) {
+            double fl, by;
+            gemm_cost(g, rows, fl, by);
+            ProfScope prof(split ? PK_GEMM_P256_SPLIT : PK_GEMM_P256, fl, by, s);
             if (split) h.p256_stagger = split_stagger(g);
             return launch_p256<F16>(h, s);
-        }
-        // upper bound of what the 256 kernel may own (a device-side row count can only be smaller: the split rule is not monotonic,
-        // so with one the launch happens whenever ANY row count up to the bound could give it rows)
-        const int hmode = g.concurrent ? 2 : 1;
+        };
+        if (g_tune[TUNE_P256_MODE] == 1) return p256(g, rows_all);
         // Host-side view of the row count: exact without m_dev; with a device-side count the caller's estimate (rows_hint: the
         // drop-in modules count the valid tokens once per mask) or else the bound M.  It only chooses between "both kernels, the
         // device evaluates the rule" and "the 128 kernel alone, no rule" -- either is correct for any actual row count.
@@ -874,45 +875,27 @@ static int launch16(const GemmArgs& g, hipStream_t s) {
         const bool plan = g.m_dev != nullptr && g.rows_plan > 0;
         const int rows_est = plan ? (int)fmin((double)g.M, g.rows_plan + 0.5)
                                   : ((g.m_dev != nullptr && g.rows_hint > 0) ? (int)fmin((double)g.M, g.rows_hint + 0.5) : g.M);
+        // upper bound of what the 256 kernel may own (a device-side row count can only be smaller: the split rule is not monotonic,
+        // so with one the launch happens whenever ANY row count up to the bound could give it rows)
         const int rows_hi = p256_rows(rows_est, g.N_pad / 256, split, hmode == 2);
-        if (plan && rows_hi >= rows_est) {
-            // every row panel of the planned count belongs to the 256 x 256 kernel: it runs ALONE over all the rows present (no rule, no
-            // tail kernel that would find nothing to do) -- correct for any actual count, like every other plan
-            gemm_cost(g, rows_all, fl, by);
-            ProfScope prof(split ? PK_GEMM_P256_SPLIT : PK_GEMM_P256, fl, by, s);
-            GemmArgs h = g;
-            if (split) h.p256_stagger = split_stagger(g);
-            return launch_p256<F16>(h, s);
-        }
+        // every row panel of the planned count belongs to the 256 x 256 kernel: it runs ALONE over all the rows present (no rule, no
+        // tail kernel that would find nothing to do) -- correct for any actual count, like every other plan
+        if (plan && rows_hi >= rows_est) return p256(g, rows_all);
         // (device-side row count: the partition is read from the table compact_rows wrote -- no table entry, no hybrid launch)
         const int ridx = p256_rule_index(g.N_pad / 256, split, hmode == 2);
         const bool can_tail = persistent_ok && (!g.stats_in || g.K == FOLD_PARTS * G_BK) &&
                               (g.m_dev == nullptr || (g.rule_table != nullptr && ridx >= 0));
         if (rows_hi > 0 && can_tail) {
-            GemmArgs h = g;
-            h.hybrid = hmode;
-            if (g.m_dev) h.rows256_dev = g.rule_table + ridx;
-            else h.rows256_host = p256_rows(g.M, g.N_pad / 256, split, hmode == 2);
-            if (split) h.p256_stagger = split_stagger(g);
+            // hybrid launch: both kernels get the same partition -- this launch's entry of the rule table, or the rule on the host
+            gt.hybrid = hmode;
+            if (g.m_dev) gt.rows256_dev = g.rule_table + ridx;
+            else gt.rows256_host = p256_rows(g.M, g.N_pad / 256, split, hmode == 2);
             const double rows_p = fmin((double)p256_rows((int)rows_all, g.N_pad / 256, split, hmode == 2), rows_all);
             rows_tail = rows_all - rows_p;
-            gemm_cost(g, rows_p, fl, by);
-            int rc;
-            {
-                ProfScope prof(split ? PK_GEMM_P256_SPLIT : PK_GEMM_P256, fl, by, s);
-                rc = launch_p256<F16>(h, s);
-            }
+            const int rc = p256(gt, rows_p);
             if (rc) return rc;
             if (g.m_dev == nullptr && rows_hi >= g.M) return 0;   // exact host-side row count and everything fitted
-            tail_only = true;
         }
-    }
-    GemmArgs gt = g;
-    gt.hybrid = tail_only ? (g.concurrent ? 2 : 1) : 0;
-    if (tail_only) {
-        const bool split = g.out_lo != nullptr;
-        if (g.m_dev) gt.rows256_dev = g.rule_table + p256_rule_index(g.N_pad / 256, split, g.concurrent != 0);
-        else gt.rows256_host = p256_rows(g.M, g.N_pad / 256, split, g.concurrent != 0);
     }
     const GemmArgs& g_ = gt;
     double fl_t, by_t;

@@ -143,11 +143,13 @@ extern "C" int bg_gemm_ex_fwd(const bg_gemm_desc* d, bg_stream_t stream) {
     BG_REQUIRE(d->out_dtype == BG_F32 || d->out_dtype == BG_BF16 || d->out_dtype == BG_F16, BG_E_DTYPE, "bg_gemm_ex_fwd: out dtype %d", d->out_dtype);
     BG_REQUIRE((d->add == nullptr || d->add_div >= 1) && (d->add2 == nullptr || d->add2_div >= 1), BG_E_ARG,
                "bg_gemm_ex_fwd: addend divisors must be >= 1");
-    bg::GemmArgs g{d->a, d->lda, d->w, d->bias, d->out, d->ldc, d->M, d->N, d->N_pad, d->K, d->out_dtype, d->act,
-                   d->add, d->ld_add, d->add ? d->add_div : 1};
-    g.add2 = d->add2; g.ld_add2 = d->ld_add2; g.add2_div = d->add2 ? d->add2_div : 1;
-    g.out_lo = d->out_lo; g.res_hi = d->res_hi; g.res_lo = d->res_lo; g.ld_res = d->ld_res;
-    g.stats_out = d->stats_out; g.stats_in = d->stats_in; g.colsum = d->colsum; g.ln_eps = d->ln_eps;
+    bg::GemmArgs g = bg::linear(d->a, d->lda, d->w, d->bias, d->out, d->ldc, d->M, d->N, d->N_pad, d->K, d->out_dtype, d->act);
+    bg::add_rows(g, d->add, d->ld_add, d->add_div);
+    bg::add2_rows(g, d->add2, d->ld_add2, d->add2_div);
+    bg::split_out(g, d->out_lo, d->stats_out);
+    bg::split_residual_in(g, d->res_hi, d->res_lo, d->ld_res);
+    bg::ln_fold_in(g, d->stats_in, d->colsum);
+    g.ln_eps = d->ln_eps;
     return bg::gemm(g, d->ab_dtype, (hipStream_t)stream);
 }
 
@@ -171,8 +173,8 @@ extern "C" int bg_conv_gemm_fwd(const bg_conv_desc* d, bg_stream_t stream) {
     BG_REQUIRE(((uintptr_t)d->x & 15) == 0 && ((uintptr_t)d->zero_page & 127) == 0, BG_E_ALIGN, "bg_conv_gemm_fwd: alignment");
     const long long rows = (long long)d->S * Ho * Wo;
     BG_REQUIRE(rows < (1ll << 31), BG_E_SHAPE, "bg_conv_gemm_fwd: too many output pixels for one call (%lld)", rows);
-    bg::GemmArgs g{d->x, d->C, d->w, d->bias, d->out, d->ldc, (int)rows, d->N, narrow ? 128 : d->N, d->kh * d->kw * d->C, BG_F32, BG_ACT_NONE,
-                   d->add, d->ld_add, 1};
+    bg::GemmArgs g = bg::linear(d->x, d->C, d->w, d->bias, d->out, d->ldc, (int)rows, d->N, narrow ? 128 : d->N, d->kh * d->kw * d->C, BG_F32);
+    bg::add_rows(g, d->add, d->ld_add, 1);
     g.cv_C = d->C; g.cv_H = d->H; g.cv_W = d->W; g.cv_kh = d->kh; g.cv_kw = d->kw; g.cv_up = d->up;
     g.cv_wo_log2 = lw; g.cv_ho_log2 = lh; g.cv_spt_log2 = ls; g.cv_zero = d->zero_page;
     return bg::gemm(g, d->dtype, (hipStream_t)stream);
@@ -186,6 +188,7 @@ extern "C" int bg_gemm_bias_act_fwd(const void* a, int lda, const void* w, const
                "bg_gemm_bias_act_fwd: bad shape M=%d N=%d N_pad=%d K=%d lda=%d ldc=%d", M, N, N_pad, K, lda, ldc);
     BG_REQUIRE(out_dtype == BG_F32 || out_dtype == BG_BF16 || out_dtype == BG_F16, BG_E_DTYPE, "bg_gemm_bias_act_fwd: out dtype %d", out_dtype);
     BG_REQUIRE(add == nullptr || add_div >= 1, BG_E_ARG, "bg_gemm_bias_act_fwd: add_div must be >= 1");
-    bg::GemmArgs g{a, lda, w, bias, out, ldc, M, N, N_pad, K, out_dtype, act, add, ld_add, add ? add_div : 1};
+    bg::GemmArgs g = bg::linear(a, lda, w, bias, out, ldc, M, N, N_pad, K, out_dtype, act);
+    bg::add_rows(g, add, ld_add, add_div);
     return bg::gemm(g, ab_dtype, (hipStream_t)stream);
 }
