@@ -5,6 +5,7 @@ Drop-in for the reference's call surface on that path only:
     DDPMScheduler / PNDMScheduler                    (schedulers.py) -> bg_cfg_ddpm_step / bg_pndm_step
     randn_tensor                                     (utils.py)
     AutoencoderKLFastDecode / AutoencoderKL1DFastDecode (vae.py)    -> bg_im2col + GEMM, bg_small_attn, ...
+    compute_cov_mmd / jsd_between_point_cloud_sets   (metrics.py)   -> bg_chamfer_pairwise / bg_occupancy_counts
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from .network import EdgePosNet, EdgeZNet, SurfPosNet, SurfZNet  # noqa: F401
@@ -16,3 +17,15 @@ from .vae import (AutoencoderKL1DFastDecode, AutoencoderKL1DFastEncode, Autoenco
 __all__ = ["SurfPosNet", "SurfZNet", "EdgePosNet", "EdgeZNet", "DDPMScheduler", "PNDMScheduler", "randn_tensor",
            "AutoencoderKLFastDecode", "AutoencoderKL1DFastDecode", "AutoencoderKLFastEncode",
            "AutoencoderKL1DFastEncode"]
+
+# pc_metric.py's surface (metrics.py), resolved on first use: `python -m brepgen_amd.metrics` must find the module not yet imported
+_METRICS = ("pairwise_chamfer", "compute_cov_mmd", "entropy_of_occupancy_grid", "jsd_between_point_cloud_sets",
+            "jensen_shannon_divergence", "normalize_pc", "read_ply")
+__all__ += list(_METRICS)
+
+
+def __getattr__(name):
+    if name in _METRICS:
+        from . import metrics
+        return getattr(metrics, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

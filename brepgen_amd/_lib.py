@@ -133,10 +133,12 @@ _SIGNATURES = {
     "bg_chamfer_offset_fit": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + [fp, fp, fp, vp]),
     "bg_philox_randn": (C.c_int, [fp, C.c_longlong, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, C.c_int, vp]),
     "bg_masked_mse": (C.c_int, [fp, fp, u8p, C.c_longlong, C.c_int, C.c_int, C.c_int, vp, fp, vp]),
+    "bg_chamfer_pairwise": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, vp]),
+    "bg_occupancy_counts": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, vp, vp, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
-ABI_VERSION = 6          # BG_ABI_VERSION of include/brepgen_hip.h this binding was written against
+ABI_VERSION = 7          # BG_ABI_VERSION of include/brepgen_hip.h this binding was written against
 
 _lib = None
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BG_ABI_VERSION 6
+#define BG_ABI_VERSION 7
 
 typedef void* bg_stream_t;              /* hipStream_t */
 
@@ -514,6 +514,29 @@ int bg_chamfer_offset_fit(const float* surf, const float* edge_pts, const int* e
  * per-row mean (the reduction of test_val, trainer.py:597), number of valid rows}.  Deterministic (no atomics). */
 int bg_masked_mse(const float* pred, const float* target, const uint8_t* row_mask, long long rows, int ld, int col0,
                   int ncols, double* scratch, float* out3, bg_stream_t stream);
+
+/* ---- evaluation metrics (pc_metric.py: COV / MMD / JSD over sets of point clouds) -------------------------------- */
+
+/* Pairwise Chamfer matrix of `_pairwise_CD` (pc_metric.py:45-80, the `chamfer_distance` CUDA extension's dl.mean(1) + dr.mean(1);
+ * the same quantity as the pure-torch distChamfer, pc_metric.py:32-42):
+ *   out[i, j] = (1/Pa) sum_p min_q |a_ip - b_jq|^2 + (1/Pb) sum_q min_p |a_ip - b_jq|^2
+ * a [S,Pa,3], b [R,Pb,3] fp32 contiguous, out [S,R] fp32; any S, R, Pa, Pb >= 1 with S * R < 2^31.  Direct-form fp32 distances
+ * (|dx|^2 then two fused multiply-adds), no floating-point atomics, fixed summation order: out[i, j] depends bitwise on cloud a_i
+ * and cloud b_j alone, not on S, R or the rest of the batch.  Coordinates must be finite.  One launch per 2^22 cloud pairs (one in all
+ * for the reference's 3000 x 1000). */
+int bg_chamfer_pairwise(const float* a, int S, int Pa, const float* b, int R, int Pb, float* out, bg_stream_t stream);
+
+/* Occupancy-grid counts of `entropy_of_occupancy_grid` (pc_metric.py:110-149) on the res^3 product grid of
+ * `unit_cube_grid_point_cloud`: pts [n_clouds,P,3] fp32, axis [res] fp32 ascending node coordinates (the host evaluates
+ * i * spacing - 1 in double and rounds to fp32, as the reference's grid does), res <= 64.  point_counts / cloud_counts [res^3]
+ * uint32, ZEROED BY THE CALLER, cell index (ix*res + iy)*res + iz:
+ *   point_counts[c] += number of points whose nearest node is c           (the reference's grid_counters)
+ *   cloud_counts[c] += number of clouds with at least one such point      (grid_bernoulli_rvars)
+ * Per axis the nearest node is decided by comparing |x - axis[i]| in double (exact for fp32 operands), which equals the reference's
+ * fp64 nearest-neighbour search over the same fp32 grid; on an exact tie the LOWER index wins (the reference's KD-tree leaves ties
+ * unspecified).  Integer atomics only: the counts are exact and do not depend on the order of execution. */
+int bg_occupancy_counts(const float* pts, int n_clouds, int P, const float* axis, int res, unsigned* point_counts,
+                        unsigned* cloud_counts, bg_stream_t stream);
 
 #ifdef __cplusplus
 }
