@@ -11,11 +11,11 @@
 //   * P^T is fed straight back as the B operand of O^T = V^T P^T: the k-slot order of the MFMA is a free
 //     permutation as long as both operands agree, so the A operand (V^T rows from LDS) is simply read in the key
 //     order the lane's score registers already have (two 8-byte reads) -- no cross-lane shuffle of P at all;
-//   * K tile in LDS: 64 keys x 128 B, LDS-DMA + 16-byte XOR swizzle (same scheme as the GEMM);
+//   * K tile in LDS: 64 keys x 128 B, LDS-DMA + 16-byte XOR swizzle (the GEMMs' scheme and helpers: gemm16.h);
 //     V tile in LDS: transposed [64 d][64 keys], row stride 68 bf16 so the 32 d-rows a half-wave reads with
 //     ds_read_b64 fall on 32 distinct bank pairs.
 // fp32 kernel: exact VALU restatement for the fp32 parity mode (not a performance path).
-#include "bg_common.h"
+#include "gemm16.h"
 #include <math.h>
 
 namespace bg {
@@ -24,23 +24,11 @@ constexpr int QKV_LD = 3 * BG_D_MODEL;     // 2304
 constexpr int VS = 68;                     // V^T row stride (bf16 elements)
 constexpr int HEAD_LDS = 64 * 128 + 64 * VS * 2;   // K tile + V^T tile bytes per head slot = 16896
 
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-template <bool F16> struct AElem;
-template <> struct AElem<false> {
-    using T = __bf16; using V8 = bf16x8; using V4 = bf16x4;
-    static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct AElem<true> {
-    using T = _Float16; using V8 = f16x8; using V4 = f16x4;
-    static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 template <int WPH, bool F16>
 __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const void* __restrict__ qkv_, const uint8_t* __restrict__ key_pad,
                                                         void* __restrict__ out_, int B, int N,
                                                         const int* __restrict__ offsets) {
-    using E = AElem<F16>;
+    using E = Elem<F16>;
     using T = typename E::T;
     using V8 = typename E::V8;
     using V4 = typename E::V4;
@@ -84,7 +72,7 @@ __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const voi
     for (int sub = 0; sub < 2; ++sub) {
         const int row = sub * 32 + (lane & 31);
         k_off[sub] = row * 128;
-        k_sw[sub] = (row >> 1) & 7;
+        k_sw[sub] = swz_term(row);
     }
 
     f32x16 o[2];
@@ -102,12 +90,10 @@ __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const voi
         for (int j = 0; j < KPI; ++j) {
             const int q = qt * KPI + j;
             const int row = q * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            const int c = dma_src_chunk(lane, row);
             int key = kt * 64 + row;
             key = key < N ? key : N - 1;
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(base + (size_t)key * QKV_LD + BG_D_MODEL + c * 8),
-                (__attribute__((address_space(3))) void*)(ktile + q * 1024), 16, 0, 0);
+            lds_dma16(base + (size_t)key * QKV_LD + BG_D_MODEL + c * 8, ktile + q * 1024);
         }
         // ---- stage V transposed ----
 #pragma unroll
@@ -226,7 +212,8 @@ __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const voi
 // ------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(4))) short v4s_t;
 
-// LDS-DMA issued from inline asm (1 KiB per wave-instruction: lane l's 16 bytes land at lds_wave_base + 16 l).  hipcc makes
+// LDS-DMA issued from inline asm (1 KiB per wave-instruction: lane l's 16 bytes land at lds_wave_base + 16 l; gemm16.h's lds_dma_piece
+// with a per-lane 64-bit address instead of base + offset).  hipcc makes
 // the first ds_read_b64_tr_b16 after a *builtin* LDS-DMA wait for vmcnt(0) -- it cannot tell that the transpose read and the
 // in-flight DMA touch different ring stages -- which would serialise the next tile's fetch with this tile's P V product.
 // Hidden in asm, the DMA is ordered by hand: counted vmcnt at the loop head, then the workgroup barrier, then the reads.
@@ -254,7 +241,7 @@ template <bool F16, bool MASKED>      // MASKED: a key-padding mask is given (de
 __global__ __launch_bounds__(256, 3) void attn16_long_kernel(const void* __restrict__ qkv_, const uint8_t* __restrict__ key_pad,
                                                              void* __restrict__ out_, int B, int N, int nqb,
                                                              const int* __restrict__ offsets, int eighths) {
-    using E = AElem<F16>;
+    using E = Elem<F16>;
     using T = typename E::T;
     using V8 = typename E::V8;
     using V4 = typename E::V4;
@@ -302,7 +289,7 @@ __global__ __launch_bounds__(256, 3) void attn16_long_kernel(const void* __restr
             int key = t * 64 + row;
             key = key < N ? key : N - 1;
             const T* src = base + (size_t)key * QKV_LD;
-            const int kc = pch ^ ((row >> 1) & 7);
+            const int kc = pch ^ ((row >> 1) & 7);       // = dma_src_chunk (gemm16.h), written out: through the helper this kernel's schedule changes
             const int vc = pch ^ (((row >> 1) & 1) << 2);
             dma16_asm(src + BG_D_MODEL + kc * 8, kbase + piece * 1024);
             dma16_asm(src + 2 * BG_D_MODEL + vc * 8, kbase + 64 * 128 + piece * 1024);
@@ -358,7 +345,7 @@ __global__ __launch_bounds__(256, 3) void attn16_long_kernel(const void* __restr
     for (int sub = 0; sub < 2; ++sub) {
         const int row = sub * 32 + (lane & 31);
         k_off[sub] = row * 128;
-        k_sw[sub] = (row >> 1) & 7;
+        k_sw[sub] = swz_term(row);
     }
     // V^T fragment addresses for the transpose read: 16-lane group g = lane >> 4 covers d columns (g & 1) * 16 .. +15 of
     // the 32-row d tile and the keys of k-chunk h = g >> 1; lane i of the group supplies the address of key (i >> 2),

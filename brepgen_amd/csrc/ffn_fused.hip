@@ -105,20 +105,14 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
         const int tid_ = ff_opaque(threadIdx.x);               \
         FF_AREGS(FF_STO)                                       \
     }
-    // (rstd, -mean rstd) of the lane's two rows (32 i + lane & 31) from the twelve partials, in the association order of every other kernel
+    // (rstd, -mean rstd) of the lane's two rows (32 i + lane & 31) from the twelve partials
     auto coeffs = [&](int r0, float2 (&cf)[2]) {
         const int l31 = ff_opaque(threadIdx.x) & 31;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             int grow = r0 + 32 * i + l31;
             grow = grow < Mv ? grow : Mv - 1;
-            float ps[16], pq[16];
-#pragma unroll
-            for (int pp = 0; pp < 16; ++pp) {
-                const float2 v = pp < FOLD_PARTS ? reinterpret_cast<const float2*>(g.stats)[(size_t)pp * g.m_stride + grow] : make_float2(0.f, 0.f);
-                ps[pp] = v.x; pq[pp] = v.y;
-            }
-            cf[i] = ln_fold_coeffs(tree16(ps), tree16(pq), FF_D, g.ln_eps);
+            cf[i] = fold_row_coeffs([&](int part) { return reinterpret_cast<const float2*>(g.stats)[(size_t)part * g.m_stride + grow]; }, FF_D, g.ln_eps);
         }
     };
 
@@ -294,25 +288,15 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
                 const float4 p0 = *reinterpret_cast<const float4*>(prow_base + ((ch ^ rsw) << 4));
                 const float4 p1 = *reinterpret_cast<const float4*>(prow_base + (((ch + 1) ^ rsw) << 4));
                 float v[8] = {p0.x + b0.x, p0.y + b0.y, p0.z + b0.z, p0.w + b0.w, p1.x + b1v.x, p1.y + b1v.y, p1.z + b1v.z, p1.w + b1v.w};
-                float fh[4], fl[4];
-                unpack4_16<F16>(make_uint2(h4.x, h4.y), fh);
-                unpack4_16<F16>(make_uint2(l4.x, l4.y), fl);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += fh[e] + fl[e];
-                unpack4_16<F16>(make_uint2(h4.z, h4.w), fh);
-                unpack4_16<F16>(make_uint2(l4.z, l4.w), fl);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 + e] += fh[e] + fl[e];
-                s8 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                q8 = ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) + ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]));
+                octet_add_residual<F16>(v, h4, l4);
+                const float2 sq = octet_stats(v);
+                s8 = sq.x; q8 = sq.y;
                 if (live) {
-                    const float va[4] = {v[0], v[1], v[2], v[3]}, vb[4] = {v[4], v[5], v[6], v[7]};
-                    uint2 ha, la, hb, lb;
-                    split4_16<F16>(va, ha, la);
-                    split4_16<F16>(vb, hb, lb);
+                    uint4 hi, lo;
+                    octet_split<F16>(v, hi, lo);
                     const unsigned o = ((unsigned)grow * FF_D + (unsigned)col) * 2u;
-                    *reinterpret_cast<uint4*>(out_hi + o) = make_uint4(ha.x, ha.y, hb.x, hb.y);
-                    *reinterpret_cast<uint4*>(out_lo + o) = make_uint4(la.x, la.y, lb.x, lb.y);
+                    *reinterpret_cast<uint4*>(out_hi + o) = hi;
+                    *reinterpret_cast<uint4*>(out_lo + o) = lo;
                 }
             };
 #pragma unroll

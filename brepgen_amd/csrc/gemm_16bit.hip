@@ -16,10 +16,7 @@
 //     16-byte-per-lane shape: lane l holds rows (l & 31), k-chunk (l >> 5) of each 16-wide k-slice;
 //   * L2 -> LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction = 8 rows x 128 B) into a ring over K,
 //     counted vmcnt + raw s_barrier, ONE barrier per 64-wide K-step;
-//   * the LDS image is XOR-swizzled at 16-byte granularity, chunk' = chunk ^ ((row >> 1) & 7).  The DMA writes
-//     lane-linear, so the permutation is applied to the per-lane SOURCE address and again on the ds_read_b128 side
-//     (same involution): every 16-lane service group of ds_read_b128 touches 16 distinct 16-byte slots of the
-//     256-byte bank row -- measured SQ_LDS_BANK_CONFLICT = 0;
+//   * the LDS image is XOR-swizzled at 16-byte granularity (gemm16.h: swz_term and the helpers around it);
 //   * fragment reads are software-pipelined one k-slice ahead of the MFMAs (order pinned with sched_barrier);
 //   * shipped kernel = the PERSISTENT one (gemm16_persistent_kernel): 2 workgroups per CU stay resident and walk
 //     the tile list, the DMA stream runs across tile seams, the epilogue works out of a small wave-private LDS patch
@@ -32,12 +29,6 @@
 #include "gemm16.h"
 
 namespace bg {
-
-__device__ __forceinline__ void lds_dma16(const void* gsrc, void* lds_wave_base) {
-    // dst = wave-uniform base + lane * 16
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // BM x BN block tile, WM x WN waves (each wave (BM/WM) x (BN/WN)), STAGES-deep LDS ring over K.
 // One barrier per K-step, all waves in lock-step.  (The 8-phase K loop that was tried here as an experimental variant in round 2
@@ -79,13 +70,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm16_kernel(GemmArgs g) {
     for (int i = 0; i < TM; ++i) {
         const int row = wm * (TM * 32) + i * 32 + (lane & 31);
         a_off[i] = row * 128;
-        a_sw[i] = (row >> 1) & 7;
+        a_sw[i] = swz_term(row);
     }
 #pragma unroll
     for (int i = 0; i < TN; ++i) {
         const int row = wn * (TN * 32) + i * 32 + (lane & 31);
         b_off[i] = BM * 128 + row * 128;
-        b_sw[i] = (row >> 1) & 7;
+        b_sw[i] = swz_term(row);
     }
     const int h = lane >> 5;
 
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm16_kernel(GemmArgs g) {
     #pragma unroll
         for (int j = 0; j < A_INSTR; ++j) {
             const int row = (wave * A_INSTR + j) * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            const int c = dma_src_chunk(lane, row);
             int grow = m0 + row;
             grow = grow < Mv ? grow : Mv - 1;                         // clamp: rows >= M are never stored
             a_src[j] = A + (size_t)grow * g.lda + c * 8;
@@ -114,7 +105,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm16_kernel(GemmArgs g) {
     #pragma unroll
         for (int j = 0; j < B_INSTR; ++j) {
             const int row = (wave * B_INSTR + j) * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            const int c = dma_src_chunk(lane, row);
             b_src[j] = W + (size_t)(n0 + row) * g.K + c * 8;
         }
         // one 1-KiB DMA piece (p < A_INSTR: activation rows, else weight rows) of K-step k0 into ring slot `stage`
@@ -271,7 +262,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm16_kernel(GemmArgs g) {
                 const float4 a4 = *reinterpret_cast<const float4*>(g.add2 + (size_t)(arow2 / g.add2_div) * g.ld_add2 + gcol);
                 v.x += a4.x; v.y += a4.y; v.z += a4.z; v.w += a4.w;
             }
-            if (g.stats_out) {                                    // per-64-column (sum, sum of squares) of the fp32 result
+            if (g.stats_out) {                                    // per-64-column (sum, sum of squares) of the fp32 result: one 4-column chunk
+                                                                  // of octet_stats' order per lane (gemm16.h), then the butterfly
                 const float s4 = (v.x + v.y) + (v.z + v.w);
                 const float q4 = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
                 const float S = group16_sum(s4), Q = group16_sum(q4);
@@ -324,15 +316,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm16_kernel(GemmArgs g) {
 //   fp32 output / residual: 32 x 32 fp32 slab per MFMA tile -> 128-byte row segments, residual added in flight.
 //   split output: 16 x 64 fp32 slab -> a lane owns 8 columns of a row: hi / lo / residual as 16-byte accesses.
 // ------------------------------------------------------------------------------------------------------
-// MODE selects the epilogue (one instantiation each, so that no instantiation carries the registers of another):
-//   P_PLAIN16  16-bit output, bias (+ReLU)                              -- QKV / FFN1 without the LayerNorm fold, VAE convs
-//   P_FOLD16   same with the LayerNorm fold (stats_in / colsum)         -- QKV / FFN1 of the denoisers
-//   P_GENERAL  fp32 or 16-bit output with fp32 addends (add / add2)     -- fp32 residual stream, embeds, VAE residuals
-//   P_SPLIT    split (hi, lo) output, addend = split residual or fp32 broadcast rows, optional row statistics
-//                                                                       -- token embeds of the denoisers (row maps, broadcast addends);
-//                                                                          out-proj / FFN2 only as the tests' baseline: the product
-//                                                                          path runs them on gemm_split.hip / gemm_p256.hip
-
+// MODE selects the epilogue: P_PLAIN16 / P_FOLD16 / P_GENERAL / P_SPLIT, described in gemm16.h.
 // CONV: the A operand is gathered from a conv window (implicit GEMM).  PURE (with CONV): the convolution as the VAE passes issue it --
 // fp32 output, fp32 residual of the same shape or none, no activation, no second addend -- with the epilogue's run-time option checks
 // folded away (same arithmetic, 904 -> 242 VALU instructions per tile epilogue).
@@ -359,34 +343,22 @@ __global__ __launch_bounds__(256, 2) void gemm16_persistent_kernel(GemmArgs g, i
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int h = lane >> 5;
-    const int nt_n = g.N_pad / BN;
-    const int G = gridDim.x;
     const int Mv = g.m_dev ? *g.m_dev : g.M;                      // rows present (compacted batch: device-side count)
     if (g.m_dev) m_panels = (Mv + BM - 1) / BM;
-    const int p0 = g.hybrid ? (g.rows256_dev ? *g.rows256_dev : g.rows256_host) >> 7 : 0;      // hybrid launches: the 256 x 256 kernel owns the panels below p0
-    // XCD-aware tile walk (block b runs on XCD b % 8; each XCD has a private 4 MiB L2): XCD x owns the row panels x, x + 8, ...;
-    // its G / 8 workgroups walk that sub-grid column-fastest, so the ~64 concurrently running tiles of an XCD share a few A row
-    // panels and keep W resident.  (Column groups per XCD, a row-major walk and adjacent-column pairing of the two workgroups of a
-    // CU were measured in rounds 1-2 and are flat or slower: DESIGN.md section 4.)
-    const int xcd = blockIdx.x & 7, w_local = blockIdx.x >> 3, cnt = G >> 3;      // G % 8 == 0 (launcher)
-    auto tile_at = [&](int t, int& tm0, int& tn0) -> bool {
-        const int panel = p0 + xcd + (t / nt_n) * 8;
-        tm0 = panel * BM;
-        tn0 = (t % nt_n) * BN;
-        return panel < m_panels;
-    };
+    const PanelWalk128 walk(g, m_panels, g.N_pad / BN, blockIdx.x, gridDim.x);
+    const int w_local = walk.w_local, cnt = walk.cnt;
 
     // per-lane DMA source rows / swizzled chunks (tile independent part)
     int a_row[A_INSTR], a_chunk[A_INSTR], b_row[B_INSTR], b_chunk[B_INSTR];
 #pragma unroll
     for (int j = 0; j < A_INSTR; ++j) {
         a_row[j] = (wave * A_INSTR + j) * 8 + (lane >> 3);
-        a_chunk[j] = ((lane & 7) ^ ((a_row[j] >> 1) & 7)) * 8;
+        a_chunk[j] = dma_src_chunk(lane, a_row[j]) * 8;
     }
 #pragma unroll
     for (int j = 0; j < B_INSTR; ++j) {
         b_row[j] = (wave * B_INSTR + j) * 8 + (lane >> 3);
-        b_chunk[j] = ((lane & 7) ^ ((b_row[j] >> 1) & 7)) * 8;
+        b_chunk[j] = dma_src_chunk(lane, b_row[j]) * 8;
     }
     const T* a_src[A_INSTR];
     const T* b_src[B_INSTR];
@@ -435,18 +407,20 @@ __global__ __launch_bounds__(256, 2) void gemm16_persistent_kernel(GemmArgs g, i
         for (int j = 0; j < B_INSTR; ++j) lds_dma16(b_src[j] + k0, sa + BM * 128 + (wave * B_INSTR + j) * 1024);
     };
 
+    // (fragment offsets and, in kstep below, the pipelined 4-slice MFMA step: gemm16_kernel's, written out a second time -- behind one
+    //  shared definition hipcc orders scalar instructions of this file's kernels differently: DESIGN.md section 4)
     int a_off[TM], a_sw[TM], b_off[TN], b_sw[TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int row = wm * 64 + i * 32 + (lane & 31);
         a_off[i] = row * 128;
-        a_sw[i] = (row >> 1) & 7;
+        a_sw[i] = swz_term(row);
     }
 #pragma unroll
     for (int i = 0; i < TN; ++i) {
         const int row = wn * 64 + i * 32 + (lane & 31);
         b_off[i] = BM * 128 + row * 128;
-        b_sw[i] = (row >> 1) & 7;
+        b_sw[i] = swz_term(row);
     }
 
     unsigned* patch = reinterpret_cast<unsigned*>(lds + RING + wave * 4096);
@@ -456,13 +430,13 @@ __global__ __launch_bounds__(256, 2) void gemm16_persistent_kernel(GemmArgs g, i
 
     int m0, n0;
     const int t_first = w_local;
-    if (!tile_at(t_first, m0, n0)) return;
+    if (!walk.tile_at(t_first, m0, n0)) return;
     set_src(m0, n0);
     issue(0, 0);
     int slot = 0;
     for (int t = t_first;; t += cnt) {
         const int cm0 = m0, cn0 = n0;                             // coordinates of the tile being computed
-        const bool has_next = tile_at(t + cnt, m0, n0);           // (m0, n0) now name the NEXT tile
+        const bool has_next = walk.tile_at(t + cnt, m0, n0);      // (m0, n0) now name the NEXT tile
         f32x16 acc[TM][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -587,12 +561,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_persistent_kernel(GemmArgs g, i
             T* out = reinterpret_cast<T*>(g.out);
             constexpr bool fold = FOLD;
             float2 cf = make_float2(1.f, 0.f);                    // (rstd, -mean * rstd) of row rbase + lane
-            if (fold) {
-                float ps[16], pq[16];
-#pragma unroll
-                for (int p = 0; p < 16; ++p) { ps[p] = st[p].x; pq[p] = st[p].y; }
-                cf = ln_fold_coeffs(tree16(ps), tree16(pq), g.K, g.ln_eps);
-            }
+            if (fold) cf = fold_row_coeffs([&](int part) { return st[part]; }, g.K, g.ln_eps);
             // every lane needs the coefficients of its 2 x 16 accumulator rows: 64 float2 go through the (not yet
             // used) patch, read back as broadcasts (all lanes of a half wave read the same address)
             float2 cAB[TM][16];
@@ -677,16 +646,8 @@ __global__ __launch_bounds__(256, 2) void gemm16_persistent_kernel(GemmArgs g, i
                     const bool row_ok = grow < Mv;
                     if (has_res) {
                         const float4 r0 = res[t & 1][2 * it], r1 = res[t & 1][2 * it + 1];
-                        if (k_res_split) {                        // x_old = hi + lo
-                            float fh[4], fl[4];
-                            unpack4_16<F16>(make_uint2(__float_as_uint(r0.x), __float_as_uint(r0.y)), fh);
-                            unpack4_16<F16>(make_uint2(__float_as_uint(r1.x), __float_as_uint(r1.y)), fl);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] += fh[e] + fl[e];
-                            unpack4_16<F16>(make_uint2(__float_as_uint(r0.z), __float_as_uint(r0.w)), fh);
-                            unpack4_16<F16>(make_uint2(__float_as_uint(r1.z), __float_as_uint(r1.w)), fl);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[4 + e] += fh[e] + fl[e];
+                        if (k_res_split) {                        // x_old = hi + lo (the loads are typed float4: either addend form)
+                            octet_add_residual<F16>(v, __builtin_bit_cast(uint4, r0), __builtin_bit_cast(uint4, r1));
                         } else {
                             v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w;
                             v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
@@ -700,22 +661,17 @@ __global__ __launch_bounds__(256, 2) void gemm16_persistent_kernel(GemmArgs g, i
                         v[4] += a1.x; v[5] += a1.y; v[6] += a1.z; v[7] += a1.w;
                     }
                     if (k_stats) {
-                        // same association order as the generic kernel: 4-column chunk partials, then a butterfly
-                        const float s8 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                        const float q8 = ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) +
-                                         ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]));
-                        const float S = group8_sum(s8), Q = group8_sum(q8);
+                        const float2 sq = octet_stats(v);
+                        const float S = group8_sum(sq.x), Q = group8_sum(sq.y);
                         // part-major [N/64][M] pairs: the 8 rows of this group are 64 contiguous bytes
                         if (row_ok && (lane & 7) == 0)
                             reinterpret_cast<float2*>(g.stats_out)[(size_t)(cbase / 64) * g.M + grow] = make_float2(S, Q);
                     }
                     if (row_ok) {
-                        const float va[4] = {v[0], v[1], v[2], v[3]}, vb[4] = {v[4], v[5], v[6], v[7]};
-                        uint2 ha, la, hb, lb;
-                        split4_16<F16>(va, ha, la);
-                        split4_16<F16>(vb, hb, lb);
-                        *reinterpret_cast<uint4*>(reinterpret_cast<T*>(g.out) + (size_t)grow * g.ldc + gcol) = make_uint4(ha.x, ha.y, hb.x, hb.y);
-                        *reinterpret_cast<uint4*>(reinterpret_cast<T*>(g.out_lo) + (size_t)grow * g.ldc + gcol) = make_uint4(la.x, la.y, lb.x, lb.y);
+                        uint4 hi, lo;
+                        octet_split<F16>(v, hi, lo);
+                        *reinterpret_cast<uint4*>(reinterpret_cast<T*>(g.out) + (size_t)grow * g.ldc + gcol) = hi;
+                        *reinterpret_cast<uint4*>(reinterpret_cast<T*>(g.out_lo) + (size_t)grow * g.ldc + gcol) = lo;
                     }
                 }
                 if (has_res && t + 2 < 4) load_res(t + 2, t & 1);

@@ -107,21 +107,15 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
     const bool relu = SPLIT ? g.act == BG_ACT_RELU : ACT == BG_ACT_RELU;
 
     // ---- LDS-DMA: wave w moves pieces w and w + 8 (8 rows x 128 B each) of every 128-row half-tile ----
-    // Source = wave-uniform base (SGPR pair: tile origin + k offset + half offset) + 32-bit per-lane byte offset; the 16-byte chunk
-    // index is XOR-swizzled on the source side (the DMA writes lane-linear), the fragment reads apply the same involution.
-    auto dma = [&](unsigned dst, const unsigned char* src, unsigned voff) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(src), "s"(dst) : "memory");
-    };
+    // Source = wave-uniform base (SGPR pair: tile origin + k offset + half offset) + 32-bit per-lane byte offset of the swizzled chunk.
     auto stage = [&](int buf, int h4, const unsigned char* src, const unsigned (&off)[2]) {
 #pragma unroll
         for (int r = 0; r < 2; ++r)
-            dma(lds0 + (unsigned)(buf * P256_BUF + h4 * P256_HALF + (wave + 8 * r) * 1024), src, off[r]);
+            lds_dma_piece(lds0 + (unsigned)(buf * P256_BUF + h4 * P256_HALF + (wave + 8 * r) * 1024), src, off[r]);
     };
     unsigned hw[2], ha[2][2];                                     // per-lane source offsets: W rows (either half), A rows per half
     auto piece_row = [&](int ln, int r) { return (wave + 8 * r) * 8 + (ln >> 3); };            // row inside the half-tile
-    auto piece_chunk = [&](int ln, int r) { return (unsigned)(((ln & 7) ^ ((piece_row(ln, r) >> 1) & 7)) * 16); };
+    auto piece_chunk = [&](int ln, int r) { return (unsigned)(dma_src_chunk(ln, piece_row(ln, r)) * 16); };
     auto a_offsets = [&](int m0t) {                               // (re)computed at every tile seam from an opaque lane id
         const int ln = opaque(threadIdx.x & 63);
         const int last = Mv - 1 - m0t;                            // rows >= Mv are clamped (never stored)
@@ -155,10 +149,10 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
     auto stage_cols = [&](int n0c) {
         const unsigned voff = (unsigned)opaque(threadIdx.x & 63) * 16u;
         if constexpr (FOLD) {
-            if (wn == 0) dma(grp_lds + 12288u, reinterpret_cast<const unsigned char*>(g.bias + n0c), voff);
-            if (wn == 1) dma(grp_lds + 13312u, reinterpret_cast<const unsigned char*>(g.colsum + n0c), voff);
+            if (wn == 0) lds_dma_piece(grp_lds + 12288u, reinterpret_cast<const unsigned char*>(g.bias + n0c), voff);
+            if (wn == 1) lds_dma_piece(grp_lds + 13312u, reinterpret_cast<const unsigned char*>(g.colsum + n0c), voff);
         } else {
-            if (has_bias) dma(patch_lds, reinterpret_cast<const unsigned char*>(g.bias + n0c), voff);
+            if (has_bias) lds_dma_piece(patch_lds, reinterpret_cast<const unsigned char*>(g.bias + n0c), voff);
         }
     };
     auto stage_rows = [&](int m0t) {
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 const int part = wn * 3 + r;
-                dma(grp_lds + (unsigned)part * 1024u, sb + (size_t)part * (size_t)g.M * 8, (unsigned)pair * 16u);
+                lds_dma_piece(grp_lds + (unsigned)part * 1024u, sb + (size_t)part * (size_t)g.M * 8, (unsigned)pair * 16u);
             }
         }
     };
@@ -179,11 +173,11 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
     // ---- fragment read addresses inside a buffer (A rows first, W rows at +32 KiB) ----
     unsigned a_rd, b_rd, xk[4];
     {
-        const int ln = threadIdx.x & 63, l31 = ln & 31, hq = ln >> 5, sw = (l31 >> 1) & 7;
+        const int ln = threadIdx.x & 63, l31 = ln & 31, hq = ln >> 5, sw = swz_term(l31);
         a_rd = (unsigned)(wm * 128 + l31) * 128u;                 // + i * 4096
         b_rd = 32768u + (unsigned)(wn * 64 + l31) * 128u;         // + j * 4096
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) xk[ks] = (unsigned)(((ks * 2 + hq) ^ sw) << 4);
+        for (int ks = 0; ks < 4; ++ks) xk[ks] = (unsigned)(((ks * 2 + hq) ^ sw) << 4);      // = frag_chunk_offsets (gemm16.h), kept local: the call changes this kernel's register allocation
     }
     f32x16 acc[4][2];
     V8 fa[2][2][4], fb[4];                                        // A sub-tiles q = 0, 1 (2 row tiles x 4 k-slices), one W sub-tile
@@ -328,7 +322,7 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
                 // columns (row tile t >> 1, rows 16 (t & 1) ..): the 32 lanes that own those rows write their eight quads; on the
                 // way back a lane owns 8 consecutive columns of a row, so the residual arrives and hi / lo leave as 16-byte
                 // accesses of whole 128-byte lines, and one 8-lane butterfly gives the row's (sum, sum of squares) -- the
-                // arithmetic, its order and the statistics layout of the 128 x 128 kernel (gemm_16bit.hip), bit for bit.
+                // octet_* helpers (gemm16.h) and the statistics layout of the 128 x 128 kernel (gemm_16bit.hip).
                 // The vector-memory counter is shared by loads and stores and the two classes retire out of order with respect to each
                 // other (a counted wait that allowed younger STORES to stay in flight passed early under load: measured,
                 // profiles/r03/gemm_p256_split_*.log).  Until round 5 the loads were therefore waited for with vmcnt(0) in three
@@ -370,20 +364,8 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
                     __builtin_amdgcn_sched_barrier(0);
                 };
                 T* out_lo = reinterpret_cast<T*>(g.out_lo);
-                // patch rows of 256 B; 16-byte chunk c XOR-swizzled by the row: ds_write_b128 and ds_read_b128 conflict-free
                 auto slab = [&](int t) {
-                    const int i = t >> 1, half = t & 1;
-                    if ((l31 >> 4) == half) {
-                        const int prow = l31 & 15;
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const int c16 = j * 8 + 2 * q + hq;
-                                *reinterpret_cast<float4*>(patch + prow * 256 + ((c16 ^ prow) << 4)) =
-                                    make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-                            }
-                    }
+                    slab_to_patch(patch, l31, hq, t & 1, acc[t >> 1]);
                     __builtin_amdgcn_wave_barrier();
 #pragma unroll
                     for (int it = 0; it < 2; ++it) {
@@ -397,33 +379,21 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
                             for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
                         }
                         const u32x4 h4 = rbuf[t % 3][it][0], l4 = rbuf[t % 3][it][1];
-                        float fh[4], fl[4];
-                        unpack4_16<F16>(make_uint2(h4[0], h4[1]), fh);
-                        unpack4_16<F16>(make_uint2(l4[0], l4[1]), fl);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] += fh[e] + fl[e];
-                        unpack4_16<F16>(make_uint2(h4[2], h4[3]), fh);
-                        unpack4_16<F16>(make_uint2(l4[2], l4[3]), fl);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[4 + e] += fh[e] + fl[e];
+                        octet_add_residual<F16>(v, make_uint4(h4[0], h4[1], h4[2], h4[3]), make_uint4(l4[0], l4[1], l4[2], l4[3]));
                         const int grow = rbase + t * 16 + prow;
                         const bool row_ok = grow < Mv;                // (in place: a clamped duplicate row must not be written)
                         if (STATS) {
-                            const float s8 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                            const float q8 = ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) +
-                                             ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]));
-                            const float S = group8_sum(s8), Q = group8_sum(q8);
+                            const float2 sq = octet_stats(v);
+                            const float S = group8_sum(sq.x), Q = group8_sum(sq.y);
                             if (row_ok && k8 == 0)
                                 reinterpret_cast<float2*>(g.stats_out)[(size_t)(cbase / 64) * g.M + grow] = make_float2(S, Q);
                         }
                         if (row_ok) {
-                            const float va[4] = {v[0], v[1], v[2], v[3]}, vb[4] = {v[4], v[5], v[6], v[7]};
-                            uint2 ha, la, hb, lb;
-                            split4_16<F16>(va, ha, la);
-                            split4_16<F16>(vb, hb, lb);
+                            uint4 hi, lo;
+                            octet_split<F16>(v, hi, lo);
                             const size_t o = (size_t)grow * g.ldc + cbase + k8 * 8;
-                            *reinterpret_cast<uint4*>(out + o) = make_uint4(ha.x, ha.y, hb.x, hb.y);
-                            *reinterpret_cast<uint4*>(out_lo + o) = make_uint4(la.x, la.y, lb.x, lb.y);
+                            *reinterpret_cast<uint4*>(out + o) = hi;
+                            *reinterpret_cast<uint4*>(out_lo + o) = lo;
                         }
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -447,18 +417,12 @@ __global__ __launch_bounds__(512) void gemm16_p256_kernel(GemmArgs g) {
                 float4 bz[2][4], cs[2][4];
                 float2 cf[4];
                 if constexpr (FOLD) {
-                    // (rstd, -mean rstd) of the lane's four rows from the staged partials, in the association order of every other
-                    // kernel (tree16 + ln_fold_coeffs); then the column vectors; then every wave of the workgroup must be done
-                    // reading before any wave's first pass overwrites its patch
+                    // (rstd, -mean rstd) of the lane's four rows from the staged partials; then the column vectors; then every wave of
+                    // the workgroup must be done reading before any wave's first pass overwrites its patch
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        float ps[16], pq[16];
-#pragma unroll
-                        for (int pp = 0; pp < 16; ++pp) {
-                            const float2 v = pp < FOLD_PARTS ? reinterpret_cast<const float2*>(grp + pp * 1024)[i * 32 + l31] : make_float2(0.f, 0.f);
-                            ps[pp] = v.x; pq[pp] = v.y;
-                        }
-                        cf[i] = ln_fold_coeffs(tree16(ps), tree16(pq), g.K, g.ln_eps);
+                        const float2* row = reinterpret_cast<const float2*>(grp) + i * 32 + l31;      // + 128 pairs per part
+                        cf[i] = fold_row_coeffs([&](int part) { return row[part * 128]; }, g.K, g.ln_eps);
                         // one row's 24 partials in registers at a time (no room for more): the pair is pinned here, or hipcc sinks the
                         // arithmetic to the pass that uses it and keeps the 24 inputs alive (spilled) until then
                         asm volatile("" : "+v"(cf[i].x), "+v"(cf[i].y) :: "memory");

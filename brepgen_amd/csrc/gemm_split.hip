@@ -21,8 +21,8 @@
 // 16-byte XOR swizzle, one barrier per K-step, two workgroups per CU (64 KiB ring + 4 x 4 KiB patches), XCD-aware tile walk.
 // The product is computed TRANSPOSED (weights as the MFMA's A operand, as in gemm_p256.hip): a lane owns one output row and four
 // consecutive columns per accumulator quad, so a 16-row x 64-column slab goes to the wave's patch as eight ds_write_b128 and
-// comes back as whole 8-column octets per lane -- the slab arithmetic (order of additions, statistics butterfly, layout of the
-// statistics) is that of the other two kernels, bit for bit (tests/test_gpu_round4.py).
+// comes back as whole 8-column octets per lane -- the slab arithmetic is the octet_* helpers of gemm16.h and the statistics layout
+// that of the other two kernels, so the results are theirs bit for bit (tests/test_gpu_round4.py).
 //
 // K-steps of a tile, KT = K / 64 = 4 chunks of KT / 4 steps; chunk c serves slab c (rows 16 c .. 16 c + 15 of the wave's 64)
 // of the PREVIOUS tile:
@@ -52,21 +52,10 @@ __global__ __launch_bounds__(256, 2) void gemm16_split_pipe_kernel(GemmArgs g, i
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hq = lane >> 5, k8 = lane & 7, r8 = lane >> 3;
-    const int nt_n = g.N_pad >> 7;
-    const int G = gridDim.x;
     const int Mv = g.m_dev ? *g.m_dev : g.M;                      // rows present (compacted batch: device-side count)
     if (g.m_dev) m_panels = (Mv + 127) >> 7;
-    // hybrid launches: the 256 x 256 kernel owns the row panels below p0 (bg_common.h p256_rows; both kernels read the same answer)
-    const int p0 = g.hybrid ? (g.rows256_dev ? *g.rows256_dev : g.rows256_host) >> 7 : 0;
-    // XCD-aware walk (block b runs on XCD b % 8, private 4 MiB L2 each): XCD x owns row panels x, x + 8, ...; its G / 8 workgroups
-    // walk that sub-grid column-fastest, so the tiles an XCD runs at a time share a few A panels and keep W resident
-    const int xcd = blockIdx.x & 7, w_local = blockIdx.x >> 3, cnt = G >> 3;                  // G % 8 == 0 (launcher)
-    auto tile_at = [&](int t, int& tm0, int& tn0) -> bool {
-        const int panel = p0 + xcd + (t / nt_n) * 8;
-        tm0 = panel << 7;
-        tn0 = (t % nt_n) << 7;
-        return panel < m_panels;
-    };
+    const PanelWalk128 walk(g, m_panels, g.N_pad >> 7, blockIdx.x, gridDim.x);
+    const int w_local = walk.w_local, cnt = walk.cnt;
 
     const unsigned char* Ab = reinterpret_cast<const unsigned char*>(g.a);
     const unsigned char* Wb = reinterpret_cast<const unsigned char*>(g.w);
@@ -75,16 +64,10 @@ __global__ __launch_bounds__(256, 2) void gemm16_split_pipe_kernel(GemmArgs g, i
     unsigned char* patch = lds + SP_RING + wave * SP_PATCH;
 
     // ---- LDS-DMA: wave w moves pieces 4 w .. 4 w + 3 (8 rows x 128 B each) of the A and of the W half of a ring slot.  Source =
-    // wave-uniform base (SGPR pair: tile origin + k offset) + per-lane byte offset; the 16-byte chunk index is XOR-swizzled on
-    // the SOURCE side (the DMA writes lane-linear), the fragment reads apply the same involution ----
-    auto dma = [&](unsigned dst, const unsigned char* src, unsigned voff) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(src), "s"(dst) : "memory");
-    };
+    // wave-uniform base (SGPR pair: tile origin + k offset) + per-lane byte offset of the swizzled 16-byte chunk ----
     unsigned va[4], vw[4];                                        // per-lane source offsets of the four A / W pieces
     auto piece_row = [&](int j) { return (wave * 4 + j) * 8 + (lane >> 3); };
-    auto piece_chunk = [&](int j) { return (unsigned)(((lane & 7) ^ ((piece_row(j) >> 1) & 7)) * 16); };
+    auto piece_chunk = [&](int j) { return (unsigned)(dma_src_chunk(lane, piece_row(j)) * 16); };
 #pragma unroll
     for (int j = 0; j < 4; ++j) vw[j] = (unsigned)piece_row(j) * ldw_b + piece_chunk(j);
     auto a_offsets = [&](int m0t) {
@@ -99,18 +82,14 @@ __global__ __launch_bounds__(256, 2) void gemm16_split_pipe_kernel(GemmArgs g, i
     auto issue = [&](int slot, const unsigned char* a_src, const unsigned char* w_src) {
         const unsigned base = lds0 + (unsigned)(slot * SP_STAGE + wave * 4096);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dma(base + (unsigned)(j * 1024), a_src, va[j]);
+        for (int j = 0; j < 4; ++j) lds_dma_piece(base + (unsigned)(j * 1024), a_src, va[j]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dma(base + (unsigned)(16384 + j * 1024), w_src, vw[j]);
+        for (int j = 0; j < 4; ++j) lds_dma_piece(base + (unsigned)(16384 + j * 1024), w_src, vw[j]);
     };
 
     // ---- fragment reads inside a ring slot (A rows first, W rows at +16 KiB) ----
     unsigned xk[4];
-    {
-        const int sw = (l31 >> 1) & 7;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) xk[ks] = (unsigned)(((ks * 2 + hq) ^ sw) << 4);
-    }
+    frag_chunk_offsets(l31, hq, xk);
     const unsigned a_rd = (unsigned)(wm * 64 + l31) * 128u;       // + i * 4096
     const unsigned b_rd = 16384u + (unsigned)(wn * 64 + l31) * 128u;
 
@@ -136,23 +115,8 @@ __global__ __launch_bounds__(256, 2) void gemm16_split_pipe_kernel(GemmArgs g, i
         b0 = *reinterpret_cast<const f32x4*>(g.bias + cbase + k8 * 8);      // (bias != null: launcher)
         b1 = *reinterpret_cast<const f32x4*>(g.bias + cbase + k8 * 8 + 4);
     };
-    // accumulators -> patch: rows of 256 B (64 fp32 columns), 16-byte chunk XOR-swizzled by the row (ds_write_b128 and
-    // ds_read_b128 conflict-free).  Transposed product: the lanes with (l31 >> 4) == half own the slab's 16 rows.
-    auto slab_write = [&](int c, const f32x16 (&p)[2][2]) {
-        const int i = c >> 1, half = c & 1;
-        if ((l31 >> 4) == half) {
-            const int prow = l31 & 15;
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int c16 = j * 8 + 2 * q + hq;
-                    *reinterpret_cast<float4*>(patch + prow * 256 + ((c16 ^ prow) << 4)) =
-                        make_float4(p[i][j][4 * q], p[i][j][4 * q + 1], p[i][j][4 * q + 2], p[i][j][4 * q + 3]);
-                }
-        }
-    };
-    // patch -> + bias + residual -> statistics -> (hi, lo): the arithmetic of gemm_16bit.hip / gemm_p256.hip, in their order
+    auto slab_write = [&](int c, const f32x16 (&p)[2][2]) { slab_to_patch(patch, l31, hq, c & 1, p[c >> 1]); };
+    // patch -> + bias + residual -> statistics -> (hi, lo)
     auto slab_finish = [&](int c, int rbase, int cbase, const sp_u32x4 (&rb)[2][2], f32x4 b0, f32x4 b1) {
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
@@ -161,31 +125,19 @@ __global__ __launch_bounds__(256, 2) void gemm16_split_pipe_kernel(GemmArgs g, i
             const float4 p1 = *reinterpret_cast<const float4*>(patch + prow * 256 + (((2 * k8 + 1) ^ prow) << 4));
             float v[8] = {p0.x + b0[0], p0.y + b0[1], p0.z + b0[2], p0.w + b0[3], p1.x + b1[0], p1.y + b1[1], p1.z + b1[2], p1.w + b1[3]};
             const sp_u32x4 h4 = rb[it][0], l4 = rb[it][1];
-            float fh[4], fl[4];
-            unpack4_16<F16>(make_uint2(h4[0], h4[1]), fh);
-            unpack4_16<F16>(make_uint2(l4[0], l4[1]), fl);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += fh[e] + fl[e];
-            unpack4_16<F16>(make_uint2(h4[2], h4[3]), fh);
-            unpack4_16<F16>(make_uint2(l4[2], l4[3]), fl);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[4 + e] += fh[e] + fl[e];
+            octet_add_residual<F16>(v, make_uint4(h4[0], h4[1], h4[2], h4[3]), make_uint4(l4[0], l4[1], l4[2], l4[3]));
             const int grow = rbase + c * 16 + prow;
             const bool row_ok = grow < Mv;                        // (in place: a clamped duplicate row must not be written)
-            const float s8 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-            const float q8 = ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) +
-                             ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]));
-            const float S = group8_sum(s8), Q = group8_sum(q8);
+            const float2 sq = octet_stats(v);
+            const float S = group8_sum(sq.x), Q = group8_sum(sq.y);
             // part-major [N / 64][M] pairs: the 8 rows of this lane group are 64 contiguous bytes
             if (row_ok && k8 == 0)
                 reinterpret_cast<float2*>(g.stats_out)[(size_t)(cbase >> 6) * g.M + grow] = make_float2(S, Q);
             if (row_ok) {
-                const float va4[4] = {v[0], v[1], v[2], v[3]}, vb4[4] = {v[4], v[5], v[6], v[7]};
-                uint2 ha, la, hb, lb;
-                split4_16<F16>(va4, ha, la);
-                split4_16<F16>(vb4, hb, lb);
+                uint4 hi, lo;
+                octet_split<F16>(v, hi, lo);
                 const size_t o = (size_t)grow * g.ldc + cbase + k8 * 8;
-                const sp_u32x4 sh = {ha.x, ha.y, hb.x, hb.y}, sl = {la.x, la.y, lb.x, lb.y};
+                const sp_u32x4 sh = {hi.x, hi.y, hi.z, hi.w}, sl = {lo.x, lo.y, lo.z, lo.w};
                 *reinterpret_cast<sp_u32x4*>(out_hi + o) = sh;
                 *reinterpret_cast<sp_u32x4*>(out_lo + o) = sl;
             }
@@ -193,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_split_pipe_kernel(GemmArgs g, i
     };
 
     int m0, n0, nm0 = 0, nn0 = 0;                                 // the tile being computed / the workgroup's next tile
-    if (!tile_at(w_local, m0, n0)) return;                        // uniform per workgroup, before any barrier
+    if (!walk.tile_at(w_local, m0, n0)) return;                   // uniform per workgroup, before any barrier
     const int KT = g.K / G_BK, CH = KT >> 2;                      // K % 256 == 0, K >= 768 (launcher): CH >= 3
     const unsigned char* a_cur = Ab + (size_t)m0 * lda_b;
     const unsigned char* w_cur = Wb + (size_t)n0 * ldw_b;
@@ -310,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_split_pipe_kernel(GemmArgs g, i
         p_cbase = n0 + wn * 64;
     };
     auto look_ahead = [&](int t) {
-        has_next = tile_at(t + cnt, nm0, nn0);
+        has_next = walk.tile_at(t + cnt, nm0, nn0);
         a_nxt = Ab + (size_t)nm0 * lda_b;
         w_nxt = Wb + (size_t)nn0 * ldw_b;
     };

@@ -140,12 +140,6 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
     const unsigned aux_lds = lds0 + QA_AUX;
     const unsigned char* aux = lds + QA_AUX;
 
-    auto dma = [&](unsigned dst, const unsigned char* src, unsigned voff) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(src), "s"(dst) : "memory");
-    };
-
     auto bar = [&]() {
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -161,7 +155,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
     // ---- LDS-DMA pieces (1 KiB = 8 rows x 128 B): wave w moves pieces w, w + 8 of each A half and piece w of each of W's q, k, v ----
     unsigned ha[2][2], hw;
     auto piece_row = [&](int ln, int r) { return (wave + 8 * r) * 8 + (ln >> 3); };
-    auto piece_chunk = [&](int ln, int r) { return (unsigned)(((ln & 7) ^ ((piece_row(ln, r) >> 1) & 7)) * 16); };
+    auto piece_chunk = [&](int ln, int r) { return (unsigned)(dma_src_chunk(ln, piece_row(ln, r)) * 16); };
     auto slot_row = [&](int grp, int tile_row) {                  // global token of a tile row (slots past a sample's end: its last token)
         if (PAIR) {                                               // slot-packed batch: the tile's rows are consecutive global rows
             const int row = grp * 256 + tile_row;
@@ -190,12 +184,12 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
         for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
             for (int r = 0; r < 2; ++r)
-                dma(lds0 + (unsigned)(buf * QA_BUF + hh * QA_AHALF + (wave + 8 * r) * 1024), src, ha[hh][r]);
+                lds_dma_piece(lds0 + (unsigned)(buf * QA_BUF + hh * QA_AHALF + (wave + 8 * r) * 1024), src, ha[hh][r]);
     };
     auto stage_w = [&](int buf, const unsigned char* src) {      // src = W + head rows + byte offset of the K-step
 #pragma unroll
         for (int c3 = 0; c3 < 3; ++c3)
-            dma(lds0 + (unsigned)(buf * QA_BUF + QA_WOFF + (wave + 8 * c3) * 1024), src + (size_t)c3 * LD * ldw_b, hw);
+            lds_dma_piece(lds0 + (unsigned)(buf * QA_BUF + QA_WOFF + (wave + 8 * c3) * 1024), src + (size_t)c3 * LD * ldw_b, hw);
     };
     // epilogue operands: statistics partials of the tile's 256 token slots ([row half][part][128 x (sum, sumsq)], 3 pieces per wave:
     // staged at the top of a tile, consumed inside its K loop), bias and column sums of the head's 192 columns (waves 0 / 1)
@@ -208,7 +202,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const int part = (wave & 3) * 3 + r;
-            dma(aux_lds + (unsigned)(gh * 12288 + part * 1024), sb + (size_t)part * (size_t)g.M * 8, (unsigned)(row >> 1) * 16u);
+            lds_dma_piece(aux_lds + (unsigned)(gh * 12288 + part * 1024), sb + (size_t)part * (size_t)g.M * 8, (unsigned)(row >> 1) * 16u);
         }
     };
     auto stage_cols = [&](int head) {
@@ -216,14 +210,15 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
         int c3 = ln >> 4;
         c3 = c3 < 3 ? c3 : 2;
         const unsigned voff = (unsigned)(c3 * LD + (ln & 15) * 4) * 4u;
-        if (wave == 0) dma(aux_lds + QA_BIAS, reinterpret_cast<const unsigned char*>(g.bias + head * 64), voff);
-        if (wave == 1) dma(aux_lds + QA_CSUM, reinterpret_cast<const unsigned char*>(g.colsum + head * 64), voff);
+        if (wave == 0) lds_dma_piece(aux_lds + QA_BIAS, reinterpret_cast<const unsigned char*>(g.bias + head * 64), voff);
+        if (wave == 1) lds_dma_piece(aux_lds + QA_CSUM, reinterpret_cast<const unsigned char*>(g.colsum + head * 64), voff);
     };
 
     // ---- fragment reads ----
     unsigned a_rd, b_rd, xk[4];
     {
-        const int ln = threadIdx.x & 63, l31 = ln & 31, hq = ln >> 5, sw = (l31 >> 1) & 7;
+        // (xk = frag_chunk_offsets and, below, fold_sums = fold_row_sums of gemm16.h, both kept local: either call changes this kernel's register allocation)
+        const int ln = threadIdx.x & 63, l31 = ln & 31, hq = ln >> 5, sw = swz_term(l31);
         a_rd = (unsigned)(wm * 64 + l31) * 128u;                  // + i * 4096
         b_rd = (unsigned)QA_WOFF + (unsigned)(wn * 96 + l31) * 128u;   // + j * 4096
 #pragma unroll
@@ -383,7 +378,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
                     // q, k and v all row-major, one 128-byte row per token slot, 16-byte chunks XOR-swizzled by the row (v was a
                     // transposed image until round 5: 64 ds_write_b16 per wave against these 16 ds_write_b64; the attention now
                     // reads it with ds_read_b64_tr_b16, as attn16_long_kernel does)
-                    *reinterpret_cast<uint2*>(lds + QA_QIMG + c3 * 32768 + R * 128 + ((((d >> 3) ^ ((R >> 1) & 7))) << 4) + (d & 7) * 2) = pk.u;
+                    *reinterpret_cast<uint2*>(lds + QA_QIMG + c3 * 32768 + R * 128 + (((d >> 3) ^ swz_term(R)) << 4) + (d & 7) * 2) = pk.u;
                     if (DBG) {
                         const int smp = grp * SPT + R / S, tok = R % S;
                         if (PAIR ? grp * 256 + R < Mv : (smp < g.B && tok < g.N))
@@ -419,7 +414,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
                 v_b8 = ((gi & 3) * 4 & 7) * 2;
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) v_c16[dt] = (dt * 32 + (gg & 1) * 16 + (gi & 3) * 4) >> 3;
-                const int sw = (l31 >> 1) & 7;
+                const int sw = swz_term(l31);
                 V8 qf[4];
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qimg + l31 * 128 + (((ks * 2 + h) ^ sw) << 4));
@@ -446,7 +441,7 @@ __global__ __launch_bounds__(512) void qkv_attn_kernel(QkvAttnArgs g) {
                         for (int r = 0; r < 16; ++r) s[r] = 0.f;
                         int kr = row0 + sub * 32 + l31;           // key row inside the slot (slot-packed: never past the slot)
                         if (PAIR) kr = kr < 63 ? kr : 63;
-                        const int ksw = PAIR ? (kr >> 1) & 7 : sw;
+                        const int ksw = PAIR ? swz_term(kr) : sw;
 #pragma unroll
                         for (int ks = 0; ks < 4; ++ks) {
                             const V8 kf = *reinterpret_cast<const V8*>(ktile + kr * 128 + (((ks * 2 + h) ^ ksw) << 4));

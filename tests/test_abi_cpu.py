@@ -391,3 +391,25 @@ def test_no_kernel_contains_op_sel_modified_packed_fp32():
         if hits:
             bad[src] = hits[:3]
     assert not bad, bad
+
+
+def test_shared_device_steps_are_defined_once():
+    """The 16-bit MFMA kernels give the same bits for the same work because they share ONE definition of each step (csrc/gemm16.h).  A
+    tripwire against pasting a copy back into a kernel: (a) the m0-saving LDS-DMA asm and (b) the octet sum-of-squares association."""
+    from brepgen_amd import build as b
+    texts = {}
+    for f in sorted(os.listdir(b.CSRC)):
+        if f.endswith((".hip", ".h")):
+            with open(os.path.join(b.CSRC, f)) as fh:
+                texts[f] = re.sub(r"//[^\n]*", "", fh.read())
+    assert "gemm16.h" in texts
+    # (a) one asm statement that saves m0, points it at the LDS destination and issues the DMA.  attn.hip: dma16_asm is the named
+    # exception -- the `off` addressing form (a per-lane 64-bit address), one user, left where it is
+    dma = re.compile(r"asm\s+volatile\s*\([^;]*s_mov_b32 m0[^;]*global_load_lds_dwordx4[^;]*\)\s*;")
+    with_dma = sorted(f for f, t in texts.items() if dma.search(t))
+    assert with_dma == ["attn.hip", "gemm16.h"], with_dma
+    assert all(len(dma.findall(texts[f])) == 1 for f in with_dma)
+    # (b) the association order of the row statistics
+    sq = "(v[0]*v[0]+v[1]*v[1])+(v[2]*v[2]+v[3]*v[3])"
+    with_sq = sorted(f for f, t in texts.items() if sq in re.sub(r"\s+", "", t))
+    assert with_sq == ["gemm16.h"], with_sq
