@@ -6,6 +6,7 @@ Drop-in for the reference's call surface on that path only:
     randn_tensor                                     (utils.py)
     AutoencoderKLFastDecode / AutoencoderKL1DFastDecode (vae.py)    -> bg_im2col + GEMM, bg_small_attn, ...
     compute_cov_mmd / jsd_between_point_cloud_sets   (metrics.py)   -> bg_chamfer_pairwise / bg_occupancy_counts
+    sample_surface / sample_meshes                   (sample_points.py) -> bg_mesh_sample
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from .network import EdgePosNet, EdgeZNet, SurfPosNet, SurfZNet  # noqa: F401
@@ -22,10 +23,16 @@ __all__ = ["SurfPosNet", "SurfZNet", "EdgePosNet", "EdgeZNet", "DDPMScheduler", 
 _METRICS = ("pairwise_chamfer", "compute_cov_mmd", "entropy_of_occupancy_grid", "jsd_between_point_cloud_sets",
             "jensen_shannon_divergence", "normalize_pc", "read_ply")
 __all__ += list(_METRICS)
+# sample_points.py's surface, likewise (`python -m brepgen_amd.sample_points`)
+_SAMPLE_POINTS = ("sample_surface", "sample_meshes", "read_stl", "write_ply")
+__all__ += list(_SAMPLE_POINTS)
 
 
 def __getattr__(name):
     if name in _METRICS:
         from . import metrics
         return getattr(metrics, name)
+    if name in _SAMPLE_POINTS:
+        from . import sample_points
+        return getattr(sample_points, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

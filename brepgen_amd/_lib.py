@@ -135,6 +135,7 @@ _SIGNATURES = {
     "bg_masked_mse": (C.c_int, [fp, fp, u8p, C.c_longlong, C.c_int, C.c_int, C.c_int, vp, fp, vp]),
     "bg_chamfer_pairwise": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, vp]),
     "bg_occupancy_counts": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, vp, vp, vp]),
+    "bg_mesh_sample": (C.c_int, [fp, vp, C.c_int, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, fp, fp, fp, vp, fp, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

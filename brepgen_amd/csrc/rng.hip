@@ -5,22 +5,9 @@
 // so an N-GPU run reproduces the 1-GPU run sample for sample without any rank drawing (or copying) noise it does not
 // use.  4 x 32 random bits -> 2 Box-Muller pairs -> 4 N(0,1) values.  HBM-bound (4 B written per element).
 #include "bg_common.h"
+#include "philox.h"
 
 namespace bg {
-
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-// u32 -> uniform in (0, 1): the top 23 bits, centred.  k + 0.5 with k < 2^23 is exactly representable in fp32 (24
-// significant bits), so the 2^23 grid points are equally spaced, none is 0 and none is 1.
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 9) + 0.5f) * (1.0f / 8388608.0f); }
 
 template <bool RAW>
 __global__ __launch_bounds__(256) void philox_randn_kernel(float* __restrict__ out, long long n_samples, int per,

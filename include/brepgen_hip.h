@@ -538,6 +538,27 @@ int bg_chamfer_pairwise(const float* a, int S, int Pa, const float* b, int R, in
 int bg_occupancy_counts(const float* pts, int n_clouds, int P, const float* axis, int res, unsigned* point_counts,
                         unsigned* cloud_counts, bg_stream_t stream);
 
+/* ---- evaluation clouds (sample_points.py: trimesh.sample.sample_surface on every generated STL) ------------------------------ */
+
+/* Area-weighted surface samples of M triangle meshes in one launch (one workgroup per mesh).
+ *   tri [T,3,3] fp32: the triangle soup of all meshes; tri_off [M+1] int32 (device): mesh m owns triangles tri_off[m] ..
+ *   tri_off[m+1]-1, tri_off[M] = T.  cdf_ws [T] fp64 workspace.  points [M,P,3] fp32, face [M,P] int32 (triangle index WITHIN its
+ *   mesh), area [M] fp64 (total surface area).
+ * Per mesh: area_k = 0.5 |(b - a) x (c - a)| in fp64 (vertices widened first) and its inclusive running sum cdf_k, formed so that it
+ * never decreases and a zero-area triangle repeats its predecessor's value exactly; area[m] = cdf_last.  Per point p with uniforms
+ * (u0, u1, u2):  x = u0 * area[m] in fp64;  face = the smallest k with cdf_k > x (zero-area triangles are never chosen; if rounding
+ * leaves no such k, the last triangle that raised the sum);  r1 = (float)u1, r2 = (float)u2, reflected (r1 = 1 - r1, r2 = 1 - r2) if
+ * r1 + r2 > 1 in fp32 (trimesh's rule);  point = (a + r1 * (b - a)) + r2 * (c - a) per coordinate in fp32, every operation rounded on
+ * its own (no fma).
+ * uniforms [M,P,3] fp64 in [0,1), or NULL: then one Philox4x32-10 block per point, key = seed, counter = (p, low 32 bits of g, draw_id,
+ * 0x5A3D0000 | bits 32..47 of g) with g = first_mesh + m the GLOBAL mesh index;  u0 = (k + 0.5) * 2^-52 with k the top 52 bits of
+ * (word0 << 32 | word1) -- exact in fp64, never 0 or 1 --, u1 / u2 = ((word >> 9) + 0.5) * 2^-23 of words 2 / 3.  A cloud depends only
+ * on (seed, draw_id, g, the mesh): a rank that owns meshes [lo, hi) passes first_mesh = lo and reproduces those clouds bit for bit.
+ * A mesh without triangles, or whose area is not finite and positive, gets area[m] as computed, face = -1 and NaN points.
+ * Device pointers, asynchronous, no allocation; M == 0 returns 0. */
+int bg_mesh_sample(const float* tri, const int* tri_off, int M, int P, unsigned long long seed, unsigned draw_id, long long first_mesh,
+                   const double* uniforms, double* cdf_ws, float* points, int* face, double* area, bg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
