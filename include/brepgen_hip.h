@@ -137,7 +137,9 @@ int bg_attn_fwd(const void* qkv, const uint8_t* key_pad, void* out, int B, int N
                 bg_stream_t stream);
 /* The same over a COMPACTED batch (variable-length execution): offsets int32 [B+1] on the device, sample b owns rows
  * offsets[b] .. offsets[b+1]-1 of qkv / out (at most N of them, every one a valid key; key_pad must then be NULL).
- * offsets == NULL is bg_attn_fwd. */
+ * offsets == NULL is bg_attn_fwd.  Every kernel takes its rows from offsets[b] .. offsets[b+1]-1 alone: rows at and beyond offsets[B]
+ * (qkv / out are usually sized for the bound B * N) are neither read nor written -- out keeps whatever it held there -- and a sample
+ * with offsets[b] == offsets[b+1] costs nothing. */
 int bg_attn_varlen_fwd(const void* qkv, const uint8_t* key_pad, void* out, int B, int N, int dtype,
                        const int* offsets, bg_stream_t stream);
 /* QKV projection with the LayerNorm fold + self-attention in ONE launch (csrc/qkv_attn.hip): sequences of an even length
