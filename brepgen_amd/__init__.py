@@ -5,6 +5,7 @@ Drop-in for the reference's call surface on that path only:
     DDPMScheduler / PNDMScheduler                    (schedulers.py) -> bg_cfg_ddpm_step / bg_pndm_step
     randn_tensor                                     (utils.py)
     AutoencoderKLFastDecode / AutoencoderKL1DFastDecode (vae.py)    -> bg_im2col + GEMM, bg_small_attn, ...
+    AutoencoderKL / AutoencoderKL1D / DiagonalGaussianDistribution (vae.py) -> the same programs + bg_vae_posterior
     compute_cov_mmd / jsd_between_point_cloud_sets   (metrics.py)   -> bg_chamfer_pairwise / bg_occupancy_counts
     sample_surface / sample_meshes                   (sample_points.py) -> bg_mesh_sample
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
@@ -26,6 +27,9 @@ __all__ += list(_METRICS)
 # sample_points.py's surface, likewise (`python -m brepgen_amd.sample_points`)
 _SAMPLE_POINTS = ("sample_surface", "sample_meshes", "read_stl", "write_ply")
 __all__ += list(_SAMPLE_POINTS)
+# the full auto-encoders of the two VAE trainers (vae.py), next to the Fast classes above
+_FULL_VAE = ("AutoencoderKL", "AutoencoderKL1D", "DiagonalGaussianDistribution")
+__all__ += list(_FULL_VAE)
 
 
 def __getattr__(name):
@@ -35,4 +39,7 @@ def __getattr__(name):
     if name in _SAMPLE_POINTS:
         from . import sample_points
         return getattr(sample_points, name)
+    if name in _FULL_VAE:
+        from . import vae
+        return getattr(vae, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

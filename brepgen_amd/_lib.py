@@ -136,6 +136,7 @@ _SIGNATURES = {
     "bg_chamfer_pairwise": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, vp]),
     "bg_occupancy_counts": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, vp, vp, vp]),
     "bg_mesh_sample": (C.c_int, [fp, vp, C.c_int, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, fp, fp, fp, vp, fp, vp]),
+    "bg_vae_posterior": (C.c_int, [fp, fp, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, fp, fp, fp, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

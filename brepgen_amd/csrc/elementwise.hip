@@ -332,9 +332,14 @@ __global__ __launch_bounds__(256) void masked_sqdiff_kernel(const float* __restr
         if (mask != nullptr && mask[r]) continue;
         const float* pa = a + r * ld + col0;
         const float* pb = b + r * ld + col0;
-        float q = 0.f;
-        for (int c = 0; c < ncols; ++c) { const float d = pa[c] - pb[c]; q += d * d; }
-        s += (double)q;
+        // fp32 over at most 64 columns at a time, fp64 across: the rows of the LDM trainers (6 .. 48 columns) are one such piece, and a
+        // whole sample as one row (the VAE trainers: 96 / 3072 columns, training.vae_loss) does not accumulate 3072 fp32 roundings
+        for (int c0 = 0; c0 < ncols; c0 += 64) {
+            const int c1 = c0 + 64 < ncols ? c0 + 64 : ncols;
+            float q = 0.f;
+            for (int c = c0; c < c1; ++c) { const float d = pa[c] - pb[c]; q += d * d; }
+            s += (double)q;
+        }
         n += 1.0;
     }
     sh[0][threadIdx.x] = s; sh[1][threadIdx.x] = n;

@@ -1,5 +1,5 @@
 // Philox4x32-10 and the 32-bit word -> uniform map, defined once for the kernels that draw on the device (rng.hip: bg_philox_randn,
-// mesh_sample.hip: bg_mesh_sample).  Every user keys the generator with the run's seed and builds its counter from GLOBAL indices plus a
+// mesh_sample.hip: bg_mesh_sample, vae_loss.hip: bg_vae_posterior).  Every user keys the generator with the run's seed and builds its counter from GLOBAL indices plus a
 // 16-bit domain tag in the top half-word of word 3, so no two users ever share a counter.  oracle/philox.py restates it in numpy.
 #pragma once
 #include "bg_common.h"
@@ -19,5 +19,23 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
 // u32 -> uniform in (0, 1): the top 23 bits, centred.  k + 0.5 with k < 2^23 is exactly representable in fp32 (24
 // significant bits), so the 2^23 grid points are equally spaced, none is 0 and none is 1.
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 9) + 0.5f) * (1.0f / 8388608.0f); }
+
+// Element block `blk` (elements 4 blk .. 4 blk + 3) of GLOBAL sample `gs` of draw `draw` of bg_philox_randn's stream (domain tag
+// 0xB9E5): one Philox block -> 2 Box-Muller pairs -> 4 N(0,1) values (RAW: the four words themselves, bit pattern in the float slots).
+// The one definition of that stream: bg_philox_randn writes it out, bg_vae_posterior consumes it in place -- same bits.
+template <bool RAW>
+__device__ __forceinline__ void philox_randn4(float (&v)[4], uint32_t blk, unsigned long long gs, uint32_t draw, uint32_t seed_lo,
+                                              uint32_t seed_hi) {
+    uint32_t c[4] = {blk, (uint32_t)gs, draw, 0xB9E50000u | (uint32_t)((gs >> 32) & 0xFFFFu)};
+    philox4x32_10(c, seed_lo, seed_hi);
+    if (RAW) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(c[j]);
+    } else {
+        const float r0 = sqrtf(-2.0f * logf(u01(c[0]))), r1 = sqrtf(-2.0f * logf(u01(c[2])));
+        const float a0 = 6.28318530717958647692f * u01(c[1]), a1 = 6.28318530717958647692f * u01(c[3]);
+        v[0] = r0 * cosf(a0); v[1] = r0 * sinf(a0); v[2] = r1 * cosf(a1); v[3] = r1 * sinf(a1);
+    }
+}
 
 }  // namespace bg

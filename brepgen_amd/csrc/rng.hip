@@ -19,17 +19,8 @@ __global__ __launch_bounds__(256) void philox_randn_kernel(float* __restrict__ o
         const long long b = i / blocks_per;
         const int blk = (int)(i - b * blocks_per);
         const unsigned long long gs = (unsigned long long)(sample0 + b);
-        uint32_t c[4] = {(uint32_t)blk, (uint32_t)gs, draw, 0xB9E50000u | (uint32_t)((gs >> 32) & 0xFFFFu)};
-        philox4x32_10(c, seed_lo, seed_hi);
         float v[4];
-        if (RAW) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(c[j]);
-        } else {
-            const float r0 = sqrtf(-2.0f * logf(u01(c[0]))), r1 = sqrtf(-2.0f * logf(u01(c[2])));
-            const float a0 = 6.28318530717958647692f * u01(c[1]), a1 = 6.28318530717958647692f * u01(c[3]);
-            v[0] = r0 * cosf(a0); v[1] = r0 * sinf(a0); v[2] = r1 * cosf(a1); v[3] = r1 * sinf(a1);
-        }
+        philox_randn4<RAW>(v, (uint32_t)blk, gs, draw, seed_lo, seed_hi);
         float* o = out + b * per + blk * 4;
         const int left = per - blk * 4;
         if (left >= 4 && (per & 3) == 0) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);

@@ -2,7 +2,8 @@
 -> ``add_noise`` -> eps-net -> masked MSE, i.e. everything ``trainer.py`` does between loading a batch and calling
 ``backward()``, and all of its ``test_val`` loops (trainer.py:374-408, 557-602, 752-797, 975-1030).  There is no backward
 pass here -- the package implements the denoising (inference) path; this module lets the same kernels compute the
-training / validation *losses* of a checkpoint.
+training / validation *losses* of a checkpoint.  ``vae_loss`` / ``vae_validation`` are the same for the two VAE trainers
+(SurfVAETrainer / EdgeVAETrainer, trainer.py:62-129, 190-259): encode -> sample the posterior -> decode -> MSE + 1e-6 KL.
 
 Every function takes and returns device tensors and enqueues on the current stream; nothing synchronises.
 """
@@ -88,3 +89,36 @@ def edge_tokens(edge_vae_encoder, edgePnt, vertPos, z_scaled=1.0):
     """trainer.py:924-933: polylines [B,S,E,32,3] -> latent tokens [B,S,E,12], concatenated with the 6 vertex
     coordinates -> the 18-channel joint data EdgeZNet denoises."""
     return torch.cat([edge_vae_encoder.encode_tokens(edgePnt) * z_scaled, vertPos], -1)
+
+
+def _vae_pass(vae, x, generator, noise):
+    """encode -> posterior.sample() -> decode, channels-last throughout: (x_cl, posterior, dec_cl, restore)."""
+    x_cl, restore = vae._points_cl(x)
+    posterior = vae._encode_cl(x_cl)
+    dec_cl = vae._decode_cl(posterior._sample_cl(generator, noise))
+    return x_cl, posterior, dec_cl, restore
+
+
+@torch.no_grad()
+def vae_loss(vae, x, generator=None, noise=None, kl_weight=1e-6):
+    """The loss of one SurfVAETrainer / EdgeVAETrainer step (trainer.py:79-86, 206-216) for a full ``AutoencoderKL`` /
+    ``AutoencoderKL1D``: mse = nn.MSELoss()(dec, x), kl = posterior.kl().mean(), total = mse + kl_weight * kl.
+
+    x: points in the datasets' layout [..., 32, 32, 3] / [..., 32, 3] or the trainers' permuted [n, 3, 32, 32] / [n, 3, 32]; ``dec``
+    comes back in the same layout.  noise [n, 3, 4, 4] / [n, 3, 4]: the posterior's eps (parity with a reference run); otherwise the
+    kernel draws it under ``sampling.noise_key(generator)`` -- deterministic: the same generator state gives the same loss."""
+    x_cl, posterior, dec_cl, restore = _vae_pass(vae, x, generator, noise)
+    n = x_cl.shape[0]
+    mse = masked_mse(dec_cl.reshape(n, -1), x_cl.reshape(n, -1))["mean"]          # rows = samples, no mask
+    kl_per_sample = posterior.kl()
+    kl = kl_per_sample.mean()
+    return {"mse": mse, "kl": kl, "total": mse + kl_weight * kl, "dec": restore(dec_cl), "kl_per_sample": kl_per_sample}
+
+
+@torch.no_grad()
+def vae_validation(vae, x, generator=None, noise=None):
+    """The body of the VAE trainers' ``test_val`` for one batch (trainer.py:118-124, 248-254): the posterior is SAMPLED, then
+    mse_sum = mse(reduction='none')(dec, x).mean(all but batch).sum() and count = len(x); the epoch's figure is sum / sum."""
+    x_cl, _, dec_cl, _ = _vae_pass(vae, x, generator, noise)
+    n = x_cl.shape[0]
+    return {"mse_sum": masked_mse(dec_cl.reshape(n, -1), x_cl.reshape(n, -1))["row_mean_sum"], "count": n}

@@ -13,6 +13,10 @@ The nn.Module tree below only holds parameters.  Like the denoisers, bf16 operan
 A pass is ONE C call: each module compiles itself (once per dtype) into a flat ``bg_vae_op`` program and ``bg_vae_run``
 enqueues every launch of it, chunking the batch against a caller-owned workspace.  (A step-by-step Python driver of the same
 primitives -- the round-1 path -- is kept as a cross-check in tests/vae_stepwise.py, outside the product module.)
+
+Below the decoders: the Fast encoders (posterior mean only), and the full ``AutoencoderKL`` / ``AutoencoderKL1D`` the VAE trainers build
+(trainer.py:20-30, 150-160), which run the same two programs with one ``bg_vae_posterior`` launch (``DiagonalGaussianDistribution``:
+sample + KL) in between.
 """
 import ctypes
 import math
@@ -603,6 +607,7 @@ class AutoencoderKLFastEncode(_HipVAE):
                  latent_channels=4, norm_num_groups=32, sample_size=32, scaling_factor=0.18215, force_upcast=True):
         super().__init__()
         self.block_out, self.latent, self.in_ch = tuple(block_out_channels), latent_channels, in_channels
+        self.n_out = latent_channels      # columns of quant_conv the program writes: the mean (AutoencoderKL: all 2 * latent moments)
         self.encoder = _Encoder2D(in_channels, latent_channels, self.block_out, layers_per_block, norm_num_groups)
         self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
 
@@ -639,7 +644,7 @@ class AutoencoderKLFastEncode(_HipVAE):
         x = pg.resnet2d(x, P, "m1", e.mid_block.resnets[1])
         x2 = pg.conv(x, P["out"], 3, 3, norm=e.conv_norm_out, act=ACT_SILU)
         pg.free(x)
-        pg.conv(x2, P["q"], 1, 1, dst=VAE_OUT, n_out=self.latent)       # DiagonalGaussianDistribution(moments).mode() = mean
+        pg.conv(x2, P["q"], 1, 1, dst=VAE_OUT, n_out=self.n_out)        # n_out = latent: DiagonalGaussianDistribution(moments).mode() = mean
         return pg
 
     def forward(self, x, return_dict=True):
@@ -653,7 +658,7 @@ class AutoencoderKLFastEncode(_HipVAE):
         dt = self._dtype()
         n, side = x_cl.shape[0], x_cl.shape[1]
         lat = side >> (len(self.block_out) - 1)
-        return self._run(x_cl, (lat, lat, self.latent), dt)
+        return self._run(x_cl, (lat, lat, self.n_out), dt)
 
     def encode_tokens(self, surfPnt):
         """Point grids [..., 32, 32, 3] (the datasets' layout) -> token-layout latents [..., 48]; equals trainer.py:519-524
@@ -675,6 +680,7 @@ class AutoencoderKL1DFastEncode(_HipVAE):
                  latent_channels=4, norm_num_groups=32, sample_size=32, scaling_factor=0.18215):
         super().__init__()
         self.block_out, self.latent, self.in_ch = tuple(block_out_channels), latent_channels, in_channels
+        self.n_out = latent_channels      # (see AutoencoderKLFastEncode)
         self.encoder = _Encoder1D(in_channels, latent_channels, self.block_out, norm_num_groups)
         self.quant_conv = nn.Conv1d(2 * latent_channels, 2 * latent_channels, 1)
 
@@ -707,7 +713,7 @@ class AutoencoderKL1DFastEncode(_HipVAE):
             x = pg.attn(x, P[f"a{i}qkv"], P[f"a{i}proj"], e.mid_block.attentions[i].group_norm, c // 32, 1.0 / math.sqrt(32))
         x2 = pg.conv(x, P["out"], 1, 3, norm=e.conv_norm_out, act=ACT_SILU)
         pg.free(x)
-        pg.conv(x2, P["q"], 1, 1, dst=VAE_OUT, n_out=self.latent)
+        pg.conv(x2, P["q"], 1, 1, dst=VAE_OUT, n_out=self.n_out)
         return pg
 
     def forward(self, sample, sample_posterior=False, return_dict=True, generator=None):
@@ -720,7 +726,7 @@ class AutoencoderKL1DFastEncode(_HipVAE):
         """Channels-last polylines [G,32,3] -> channels-last latent modes [G,4,3]."""
         dt = self._dtype()
         n = x_cl.shape[0]
-        return self._run(x_cl, (x_cl.shape[1] >> len(self.block_out), self.latent), dt)
+        return self._run(x_cl, (x_cl.shape[1] >> len(self.block_out), self.n_out), dt)
 
     def encode_tokens(self, edgePnt):
         """Polylines [..., 32, 3] -> token-layout latents [..., 12]; equals trainer.py:924-929
@@ -731,3 +737,236 @@ class AutoencoderKL1DFastEncode(_HipVAE):
         x_cl = edgePnt.detach().to(torch.float32).reshape(-1, *edgePnt.shape[-2:]).contiguous()
         z = self._encode_cl(x_cl)                                  # [G, 4, latent]
         return z.reshape(*lead, z.shape[1] * z.shape[2])
+
+
+# --------------------------------------------------------------------------------------------------
+# full auto-encoders (what SurfVAETrainer / EdgeVAETrainer train, validate and save: trainer.py:20-30, 150-160)
+# --------------------------------------------------------------------------------------------------
+class AutoencoderKLOutput:
+    def __init__(self, latent_dist):
+        self.latent_dist = latent_dist
+
+
+class DecoderOutput:
+    def __init__(self, sample):
+        self.sample = sample
+
+
+def _to_ref(t_cl):
+    """Channels-last [n, *spatial, C] -> the reference's [n, C, *spatial]."""
+    return t_cl.movedim(-1, 1).contiguous()
+
+
+def _to_cl(t):
+    return t.movedim(1, -1).contiguous()
+
+
+class DiagonalGaussianDistribution:
+    """The posterior ``encode`` returns (diffusers' class of that name, network.py:513-514): ``parameters`` [n, 2L, ...] = mean | log-variance.
+
+    ``sample`` and ``kl`` -- what the trainers call -- are ONE ``bg_vae_posterior`` launch on the channels-last moments the encode
+    program wrote; the launch that samples also leaves the clamped log-variance and the KL behind, so ``kl()`` after ``sample()`` costs
+    nothing.  ``mean`` / ``logvar`` / ``std`` / ``var`` are the reference's attributes for callers that read them (``logvar`` is the kernel's
+    clamped output, ``std`` / ``var`` its exponentials); nothing on the package's own paths does."""
+
+    def __init__(self, parameters, deterministic=False):
+        if deterministic:
+            raise NotImplementedError("BrepGen never builds a deterministic posterior")
+        self._init_cl(_to_cl(parameters.detach().to(torch.float32)))
+
+    @classmethod
+    def _from_cl(cls, moments_cl):
+        self = cls.__new__(cls)
+        self._init_cl(moments_cl)
+        return self
+
+    def _init_cl(self, moments_cl):
+        self._mom = moments_cl                                     # [n, *spatial, 2L] fp32
+        self.latent = moments_cl.shape[-1] // 2
+        self._lv_cl = self._kl = None
+
+    def _launch(self, noise, seed, draw_id, first_sample):
+        m = self._mom
+        if not m.is_cuda:
+            raise _lib.BrepgenHipError(f"brepgen_amd VAE posterior runs on the MI355X only (tensor on {m.device})")
+        n, L = m.shape[0], self.latent
+        P = math.prod(m.shape[1:-1])
+        if noise is not None:
+            if tuple(noise.shape) != (n, L, *m.shape[1:-1]):
+                raise ValueError(f"noise has shape {tuple(noise.shape)}, the posterior's mean {(n, L, *m.shape[1:-1])}")
+            noise = noise.detach().to(device=m.device, dtype=torch.float32).contiguous()
+        z = torch.empty(*m.shape[:-1], L, device=m.device, dtype=torch.float32)
+        lv, kl = torch.empty_like(z), torch.empty(n, device=m.device, dtype=torch.float32)
+        check(_lib.load().bg_vae_posterior(ptr(m), ptr(noise), n, P, L, int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_id) & 0xFFFFFFFF,
+                                           int(first_sample), ptr(z), ptr(lv), ptr(kl), stream()), "bg_vae_posterior")
+        self._lv_cl, self._kl = lv, kl                              # (neither depends on the noise)
+        return z
+
+    def _sample_cl(self, generator=None, noise=None, seed=None, draw_id=0, first_sample=0):
+        if noise is None and seed is None:
+            from .sampling import noise_key
+            seed = noise_key(generator)
+        return self._launch(noise, 0 if seed is None else seed, draw_id, first_sample)
+
+    def sample(self, generator=None, *, noise=None, seed=None, draw_id=0, first_sample=0):
+        """z = mean + std * eps, [n, L, ...].  ``noise`` [n, L, ...] given: it is eps (the parity mode -- the reference draws from the device's
+        global RNG, which no other platform reproduces).  Otherwise the kernel draws eps itself: element e of row b is
+        ``sampling.device_randn``'s value for (key, draw_id, first_sample + b, e), key = ``seed`` or else ``sampling.noise_key(generator)``
+        -- the generator's STATE, which this call does not advance: successive draws under one key take successive ``draw_id``s.  A rank
+        that owns rows [lo, hi) of a batch passes first_sample = lo and gets those rows of the single-GPU draw."""
+        return _to_ref(self._sample_cl(generator, noise, seed, draw_id, first_sample))
+
+    def mode(self):
+        return self.mean
+
+    def kl(self, other=None):
+        """0.5 * sum(mean^2 + var - 1 - logvar) over every non-batch dimension, [n] (trainer.py:84; EdgeVAETrainer's hand-written
+        sum over [1, 2], trainer.py:211-214, is the same quantity)."""
+        if other is not None:
+            raise NotImplementedError("BrepGen only takes the KL to N(0, I)")
+        if self._kl is None:
+            self._launch(None, 0, 0, 0)                             # (the draw is discarded: one launch yields z, logvar and kl)
+        return self._kl
+
+    @property
+    def parameters(self):
+        return _to_ref(self._mom)
+
+    @property
+    def mean(self):
+        return _to_ref(self._mom[..., :self.latent])
+
+    @property
+    def logvar(self):
+        if self._lv_cl is None:
+            self._launch(None, 0, 0, 0)
+        return _to_ref(self._lv_cl)
+
+    @property
+    def std(self):
+        return torch.exp(0.5 * self.logvar)
+
+    @property
+    def var(self):
+        return torch.exp(self.logvar)
+
+
+def _on_runners(name):
+    """An attribute of the full module that lives on its two program runners."""
+    def get(self):
+        return getattr(self._runners[0], name)
+
+    def put(self, value):
+        for r in self._runners:
+            setattr(r, name, value)
+    return property(get, put)
+
+
+class _FullVAE(nn.Module):
+    """encoder + quant_conv + post_quant_conv + decoder under the checkpoint's own keys.  The networks are not written again: the
+    module owns one Fast encoder (widened to all 2 * latent moments) and one Fast decoder as its two program runners and registers
+    THEIR sub-modules as its own, so a full checkpoint loads ``strict=True`` and ``state_dict()`` is what the Fast classes load."""
+    _ENC = _DEC = None
+
+    def _build(self, cfg):
+        enc, dec = self._ENC(**cfg), self._DEC(**cfg)
+        enc.n_out = 2 * enc.latent
+        self.latent, self.in_ch = enc.latent, enc.in_ch
+        self.encoder, self.quant_conv = enc.encoder, enc.quant_conv
+        self.decoder, self.post_quant_conv = dec.decoder, dec.post_quant_conv
+        self._runners = (enc, dec)                                   # (a tuple: not registered, no keys of their own)
+
+    def _stale(self, workspaces):
+        for r in self._runners:
+            r._packs, r._programs = {}, {}
+            if workspaces:
+                r._ws = {}
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._stale(True)
+        return out
+
+    def load_state_dict(self, *a, **k):
+        self._stale(False)
+        return super().load_state_dict(*a, **k)
+
+    def release_workspace(self):
+        for r in self._runners:
+            r.release_workspace()
+
+    # switches of _HipVAE, set on both runners
+    compute_dtype, WS_BUDGET, two_streams = _on_runners("compute_dtype"), _on_runners("WS_BUDGET"), _on_runners("two_streams")
+
+    def _check(self, t, what):
+        if not t.is_cuda:
+            raise _lib.BrepgenHipError(f"brepgen_amd VAE {what} runs on the MI355X only (tensor on {t.device})")
+
+    def _points_cl(self, x):
+        """Points in the datasets' layout [..., (32,) 32, 3] or the trainers' permuted [n, 3, (32,) 32] -> (channels-last [N, (32,) 32, 3],
+        restore), restore(y_cl) giving y in x's layout.  The last dimension decides: in_channels long = the datasets' layout."""
+        self._check(x, "encode")
+        rank = self._RANK
+        x = x.detach().to(torch.float32)
+        if x.shape[-1] == self.in_ch and x.dim() >= rank + 1:
+            lead = x.shape[:-(rank + 1)]
+            return x.reshape(-1, *x.shape[-(rank + 1):]).contiguous(), lambda y: y.reshape(*lead, *y.shape[1:])
+        if x.dim() != rank + 2 or x.shape[1] != self.in_ch:
+            raise ValueError(f"{type(self).__name__}: points of shape {tuple(x.shape)}")
+        return _to_cl(x), _to_ref
+
+    def _encode_cl(self, x_cl):
+        return DiagonalGaussianDistribution._from_cl(self._runners[0]._encode_cl(x_cl))
+
+    def _decode_cl(self, z_cl):
+        return self._runners[1]._decode_cl(z_cl)
+
+    def encode(self, x, return_dict=True):
+        self._check(x, "encode")
+        posterior = self._encode_cl(_to_cl(x.detach().to(torch.float32)))
+        return AutoencoderKLOutput(posterior) if return_dict else (posterior,)
+
+    def decode(self, z, return_dict=True):
+        self._check(z, "decode")
+        dec = _to_ref(self._decode_cl(_to_cl(z.detach().to(torch.float32))))
+        return DecoderOutput(dec) if return_dict else (dec,)
+
+    def forward(self, sample, sample_posterior=False, return_dict=True, generator=None, *, noise=None):
+        """network.py:660-687: encode, sample the posterior (or take its mode), decode -- the encode program, one bg_vae_posterior and the
+        decode program on the current stream, channels-last in between."""
+        self._check(sample, "forward")
+        posterior = self._encode_cl(_to_cl(sample.detach().to(torch.float32)))
+        if sample_posterior:
+            z_cl = posterior._sample_cl(generator, noise)
+        else:
+            z_cl = posterior._mom[..., :self.latent].contiguous()
+        dec = _to_ref(self._decode_cl(z_cl))
+        return DecoderOutput(dec) if return_dict else (dec,)
+
+
+class AutoencoderKL(_FullVAE):
+    """Surface VAE (trainer.py:20-30; network.py AutoencoderKL): points [F,3,32,32] <-> posterior over [F,3,4,4]."""
+    _ENC, _DEC, _RANK = AutoencoderKLFastEncode, AutoencoderKLFastDecode, 2
+
+    def __init__(self, in_channels=3, out_channels=3, down_block_types=("DownEncoderBlock2D",),
+                 up_block_types=("UpDecoderBlock2D",), block_out_channels=(64,), layers_per_block=1, act_fn="silu",
+                 latent_channels=4, norm_num_groups=32, sample_size=32, scaling_factor=0.18215, force_upcast=True):
+        super().__init__()
+        self._build(dict(in_channels=in_channels, out_channels=out_channels, down_block_types=down_block_types,
+                         up_block_types=up_block_types, block_out_channels=block_out_channels, layers_per_block=layers_per_block,
+                         act_fn=act_fn, latent_channels=latent_channels, norm_num_groups=norm_num_groups, sample_size=sample_size,
+                         scaling_factor=scaling_factor, force_upcast=force_upcast))
+
+
+class AutoencoderKL1D(_FullVAE):
+    """Edge VAE (trainer.py:150-160; network.py AutoencoderKL1D): points [G,3,32] <-> posterior over [G,3,4]."""
+    _ENC, _DEC, _RANK = AutoencoderKL1DFastEncode, AutoencoderKL1DFastDecode, 1
+
+    def __init__(self, in_channels=3, out_channels=3, down_block_types=("DownEncoderBlock2D",),
+                 up_block_types=("UpDecoderBlock2D",), block_out_channels=(64,), layers_per_block=1, act_fn="silu",
+                 latent_channels=4, norm_num_groups=32, sample_size=32, scaling_factor=0.18215):
+        super().__init__()
+        self._build(dict(in_channels=in_channels, out_channels=out_channels, down_block_types=down_block_types,
+                         up_block_types=up_block_types, block_out_channels=block_out_channels, layers_per_block=layers_per_block,
+                         act_fn=act_fn, latent_channels=latent_channels, norm_num_groups=norm_num_groups, sample_size=sample_size,
+                         scaling_factor=scaling_factor))

@@ -513,7 +513,9 @@ int bg_chamfer_offset_fit(const float* surf, const float* edge_pts, const int* e
 /* Masked MSE of the trainers' loss / validation forward (trainer.py:354, 538, 597, 950-952; `loss_fn(pred[~mask],
  * noise[~mask])`): pred / target fp32 [rows, ld], row_mask uint8 [rows] (1 = padded, skipped) or NULL, columns
  * [col0, col0+ncols).  scratch: 1024 doubles.  out3 (device): {mean over valid elements, sum over valid rows of the
- * per-row mean (the reduction of test_val, trainer.py:597), number of valid rows}.  Deterministic (no atomics). */
+ * per-row mean (the reduction of test_val, trainer.py:597), number of valid rows}.  A row is summed in fp32 over pieces of 64 columns
+ * and in fp64 across pieces and rows, so a whole sample can be one row (the VAE trainers, trainer.py:85, 122: rows = samples, no
+ * mask).  Deterministic (no atomics). */
 int bg_masked_mse(const float* pred, const float* target, const uint8_t* row_mask, long long rows, int ld, int col0,
                   int ncols, double* scratch, float* out3, bg_stream_t stream);
 
@@ -560,6 +562,24 @@ int bg_occupancy_counts(const float* pts, int n_clouds, int P, const float* axis
  * Device pointers, asynchronous, no allocation; M == 0 returns 0. */
 int bg_mesh_sample(const float* tri, const int* tri_off, int M, int P, unsigned long long seed, unsigned draw_id, long long first_mesh,
                    const double* uniforms, double* cdf_ws, float* points, int* face, double* area, bg_stream_t stream);
+
+/* ---- full VAEs (trainer.py:11-264: SurfVAETrainer / EdgeVAETrainer train and validate the auto-encoders whose checkpoints the
+ * decoders above load) ------------------------------------------------------------------------------------------------------- */
+
+/* diffusers' DiagonalGaussianDistribution on the encoder's moments (network.py:513-514), as the two VAE trainers use it between
+ * `encode` and `decode` (trainer.py:79-84, 118-119, 206-214, 248-249): sample the posterior and its KL to N(0, I) in one launch.
+ *   moments [n, P, 2L] fp32 channels-last (what the encode programs write): channels 0 .. L-1 the mean, L .. 2L-1 the log-variance.
+ *   lv = clamp(logvar, -30, 20);  std = expf(0.5f * lv);  z = mean + std * eps  (fp32, the product and the sum rounded separately);
+ *   kl[b] = 0.5 * sum over the P * L elements of sample b of (mean^2 + exp(lv) - 1 - lv): every term formed in fp64 from the fp32
+ *   inputs (as mean^2 + (expm1(lv) - lv)), summed in fp64 in an order fixed by P * L alone, rounded to fp32 once.  No atomics: a
+ *   sample's z, lv and kl are the same bits in any batch and any call.
+ * noise [n, L, P] fp32 (the reference's N,C,... order: what randn(mean.shape) gives), or NULL: then element e = c * P + p of sample b
+ * is exactly what bg_philox_randn gives for (seed, draw_id, first_sample + b, e) with per_sample = P * L -- a rank that owns samples
+ * [lo, hi) passes first_sample = lo and reproduces those rows of the single-GPU draw.
+ * z_out [n, P, L] channels-last (what the decode programs take); logvar_out [n, P, L] (optional): the CLAMPED log-variance;
+ * kl_out [n] (optional).  Any P * L >= 1 that fits an int.  n == 0 returns 0 without a launch. */
+int bg_vae_posterior(const float* moments, const float* noise, long long n, int P, int L, unsigned long long seed, unsigned draw_id,
+                     long long first_sample, float* z_out, float* logvar_out, float* kl_out, bg_stream_t stream);
 
 #ifdef __cplusplus
 }
