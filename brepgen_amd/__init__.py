@@ -8,6 +8,7 @@ Drop-in for the reference's call surface on that path only:
     AutoencoderKL / AutoencoderKL1D / DiagonalGaussianDistribution (vae.py) -> the same programs + bg_vae_posterior
     compute_cov_mmd / jsd_between_point_cloud_sets   (metrics.py)   -> bg_chamfer_pairwise / bg_occupancy_counts
     sample_surface / sample_meshes                   (sample_points.py) -> bg_mesh_sample
+    CADStore / augment_points (dataset.py: load_data, the six datasets) (dataset.py) -> bg_cad_filter / bg_batch_plan / bg_batch_gather
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from .network import EdgePosNet, EdgeZNet, SurfPosNet, SurfZNet  # noqa: F401
@@ -30,6 +31,9 @@ __all__ += list(_SAMPLE_POINTS)
 # the full auto-encoders of the two VAE trainers (vae.py), next to the Fast classes above
 _FULL_VAE = ("AutoencoderKL", "AutoencoderKL1D", "DiagonalGaussianDistribution")
 __all__ += list(_FULL_VAE)
+# dataset.py's surface (dataset.py): the training batches of the six trainers, assembled on the device
+_DATASET = ("CADStore", "augment_points")
+__all__ += list(_DATASET)
 
 
 def __getattr__(name):
@@ -42,4 +46,7 @@ def __getattr__(name):
     if name in _FULL_VAE:
         from . import vae
         return getattr(vae, name)
+    if name in _DATASET:
+        from . import dataset
+        return getattr(dataset, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

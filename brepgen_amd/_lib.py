@@ -78,6 +78,21 @@ class VaeOp(C.Structure):             # bg_vae_op
                 ("n_pad2", C.c_int), ("w2_dtype", C.c_int), ("w2", vp), ("bias2", fp)]
 
 
+class CadStore(C.Structure):         # bg_cad_store
+    _fields_ = [("surf_ncs", fp), ("surf_pos", fp), ("edge_ncs", fp), ("edge_pos", fp), ("corner_wcs", fp),
+                ("face_off", vp), ("edge_off", vp), ("adj_off", vp), ("adj_idx", vp),
+                ("n_records", C.c_int), ("n_faces", C.c_int), ("n_edges", C.c_int), ("n_adj", C.c_int)]
+
+
+class BatchDraws(C.Structure):       # bg_batch_draws
+    _fields_ = [("u", fp), ("turns", vp), ("face_key1", vp), ("face_key2", vp), ("edge_key1", vp), ("edge_key2", vp)]
+
+
+class BatchOut(C.Structure):         # bg_batch_out
+    _fields_ = [("surf_pos", fp), ("surf_ncs", fp), ("surf_mask", u8p), ("edge_pos", fp), ("edge_ncs", fp), ("edge_mask", u8p),
+                ("vertex_pos", fp)]
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("kernel", C.c_char_p), ("launches", C.c_int), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -137,6 +152,12 @@ _SIGNATURES = {
     "bg_occupancy_counts": (C.c_int, [fp, C.c_int, C.c_int, fp, C.c_int, vp, vp, vp]),
     "bg_mesh_sample": (C.c_int, [fp, vp, C.c_int, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, fp, fp, fp, vp, fp, vp]),
     "bg_vae_posterior": (C.c_int, [fp, fp, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, fp, fp, fp, vp]),
+    "bg_cad_filter": (C.c_int, [C.POINTER(CadStore), C.c_int, C.c_int, C.c_float, C.c_double, u8p, vp]),
+    "bg_batch_plan": (C.c_int, [C.POINTER(CadStore), vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_uint,
+                                C.POINTER(BatchDraws), vp, vp, vp, fp, vp]),
+    "bg_batch_gather": (C.c_int, [C.POINTER(CadStore), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, fp,
+                                  C.POINTER(BatchOut), vp]),
+    "bg_points_rotate_normalize": (C.c_int, [fp, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, fp, vp, fp, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

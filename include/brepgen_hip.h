@@ -581,6 +581,103 @@ int bg_mesh_sample(const float* tri, const int* tri_off, int M, int P, unsigned 
 int bg_vae_posterior(const float* moments, const float* noise, long long n, int P, int L, unsigned long long seed, unsigned draw_id,
                      long long first_sample, float* z_out, float* logvar_out, float* kl_out, bg_stream_t stream);
 
+/* ---- training batches (dataset.py: filter_data / load_data, SurfPosData .. EdgeZData.__getitem__, SurfData / EdgeData; utils.py
+ * pad_repeat, pad_zero, rotate_axis, get_bbox, rotate_point_cloud) ------------------------------------------------------------- */
+
+/* N records packed once on the device (a HOST struct of device pointers).  Record r owns faces face_off[r] .. face_off[r+1]-1 and edges
+ * edge_off[r] .. edge_off[r+1]-1; GLOBAL face g owns adj_idx[adj_off[g] .. adj_off[g+1]-1], the pickles' faceEdge_adj: edge ids LOCAL
+ * to the record.  surf_ncs / edge_ncs 16-byte aligned. */
+typedef struct bg_cad_store {
+    const float* surf_ncs;      /* [n_faces, 32, 32, 3] */
+    const float* surf_pos;      /* [n_faces, 6]      surf_bbox_wcs */
+    const float* edge_ncs;      /* [n_edges, 32, 3] */
+    const float* edge_pos;      /* [n_edges, 6]      edge_bbox_wcs */
+    const float* corner_wcs;    /* [n_edges, 2, 3] */
+    const int* face_off;        /* [n_records + 1] */
+    const int* edge_off;        /* [n_records + 1] */
+    const int* adj_off;         /* [n_faces + 1] */
+    const int* adj_idx;         /* [n_adj] */
+    int n_records, n_faces, n_edges, n_adj;
+} bg_cad_store;
+
+/* Recorded draws that replace the device's Philox draws in the plan (all device pointers; a NULL member reads as u = 0, turns = 1, keys
+ * = 0, i.e. not augmented / the identity permutation).  Key arrays are indexed by the source face's LOCAL index and the position in its
+ * adjacency list; only the first F (or degree) entries of the *1 arrays are read, all max_face (max_edge) entries of the *2 arrays, and
+ * those only where there is a second shuffle (face_key2: SurfPos, edge_key2: EdgePos).  To replay a permutation p (out[i] = in[p[i]])
+ * pass key[p[i]] = i. */
+typedef struct bg_batch_draws {
+    const double* u;            /* [B]       augment iff aug && u > 0.5 */
+    const int* turns;           /* [B, 3]    quarter turns about x, y, z, each in 1 .. 3 */
+    const uint32_t* face_key1;  /* [B, S] */
+    const uint32_t* face_key2;  /* [B, S] */
+    const uint32_t* edge_key1;  /* [B, S, E] */
+    const uint32_t* edge_key2;  /* [B, S, E] */
+} bg_batch_draws;
+
+/* Output tensors of a batch; only the members of the kind are read (see the gather entry below). */
+typedef struct bg_batch_out {
+    float* surf_pos;            /* [B, S, 6] */
+    float* surf_ncs;            /* [B, S, 32, 32, 3] */
+    uint8_t* surf_mask;         /* [B, S]        1 = padding */
+    float* edge_pos;            /* [B, S, E, 6] */
+    float* edge_ncs;            /* [B, S, E, 32, 3] */
+    uint8_t* edge_mask;         /* [B, S, E]     1 = padding */
+    float* vertex_pos;          /* [B, S, E, 6] */
+} bg_batch_out;
+
+/* dataset.py:22-81 filter_data for all records, one workgroup each: keep[r] = 0 iff the record has more than max_face faces, a face
+ * with more than max_edge or with 0 edges, two face boxes that are "the same", or two edge boxes in one face's adjacency list that are
+ * "the same"; a and b are the same iff |fp32(a_k * scale) - fp32(b_k * scale)| < (float)threshold in fp32 for all six k (numpy compares
+ * the fp32 array with the Python float that way; a NaN is never the same).  The reference's greedy non_repeat loop rejects exactly when
+ * ANY pair i < j is the same, so this is an all-pairs test without order dependence.  A record whose adjacency refers outside the
+ * record is not kept.  keep [n_records] uint8; n_records == 0 returns 0 without a launch. */
+int bg_cad_filter(const bg_cad_store* store, int max_face, int max_edge, float scale, double threshold, uint8_t* keep,
+                  bg_stream_t stream);
+
+/* The slot maps of one batch, one workgroup per CAD.  idx [B] int32 (device): GLOBAL record numbers; kind = BG_SURFPOS .. BG_EDGEZ;
+ * S = max_face <= 512, E = max_edge, S * E <= 4096.
+ *   face_src [B, S] int32: row of the store's face arrays that slot s copies, -1 = zero padding;
+ *   edge_src [B, S, E] int32 (edge kinds): row of the edge arrays, -1 = zero padding;
+ *   rot [B] int32: 0 = not augmented, else qx | qy << 2 | qz << 4 with the quarter turns about x, y, z in 1 .. 3;
+ *   scale [B, 3] fp64: max |.| over the CAD's surf_pos, edge_pos, corner_wcs (an fp32 max-abs, exact, widened).
+ * A permutation is the stable argsort of uint32 keys (out[i] = in[argsort(key)[i]]); pad_repeat(n -> L): r = L div n, sep = L - r n,
+ * slot i < sep (r + 1) takes source i div (r + 1), any other slot sep + (i - sep (r + 1)) div r.
+ *   SurfPos: faces shuffle -> pad_repeat(S) -> second shuffle over the S slots.
+ *   SurfZ:   faces shuffle -> pad_zero.
+ *   EdgePos: per face (original order) edges shuffle -> pad_repeat(E) -> second shuffle; faces shuffle -> pad_zero (all -1 rows).
+ *   EdgeZ:   per face edges shuffle -> pad_zero; faces shuffle -> pad_zero.
+ * draws == NULL: Philox4x32-10, key = seed, counter = (element, record number, draw_id, 0xDA7A0000 | tag) with tag = 0 and element =
+ * local face i for the face keys (word 0 = key 1, word 1 = key 2), tag = f + 1 and element = adjacency position j for the edge keys
+ * of local face f, tag = 0 and element = 0xFFFFFFFF for the CAD's own block: u = ((word0 >> 9) + 0.5) * 2^-23, turn k = 1 +
+ * ((word_(1+k) * 3) >> 32).  Nothing depends on the position in the batch: a record's slice is the same in any batch.
+ * A record with more than S faces or a degree above E is cut to fit and one outside the store gives all -1 (the caller checks on the
+ * host; the kernel only stays in bounds).  B == 0 returns 0. */
+int bg_batch_plan(const bg_cad_store* store, const int* idx, int B, int kind, int max_face, int max_edge, int aug,
+                  unsigned long long seed, unsigned draw_id, const bg_batch_draws* draws, int* face_src, int* edge_src, int* rot,
+                  double* scale, bg_stream_t stream);
+
+/* The batch tensors of `kind` from a plan, one launch; EVERY element of every output of the kind is written (padding +0.0, masks 0 / 1):
+ *   SurfPos: surf_pos.  SurfZ: surf_pos, surf_ncs, surf_mask.  EdgePos: edge_pos, surf_ncs, surf_pos, surf_mask.
+ *   EdgeZ: edge_ncs, edge_pos, edge_mask, surf_ncs, surf_pos, vertex_pos.
+ * rot[b] == 0: grids are bitwise copies; boxes and corners are x * bbox_scaled in fp32; each edge's corner pair is ordered
+ * lexicographically by (x, y, z) on those values (np.lexsort; a full tie keeps the order).
+ * rot[b] != 0: the composed rotation is applied as the signed coordinate permutation it is (a negated zero becomes +0.0).  Grids:
+ * rotated only.  Boxes: both corners rotated, divided by the CAD's scale of that array in fp64, per-axis min / max, times bbox_scaled
+ * in fp64, rounded to fp32 once.  Corners: rotated, / scale, * bbox_scaled in fp64, the pair ordered on the fp64 values, rounded once.
+ * Source rows outside the store count as padding. */
+int bg_batch_gather(const bg_cad_store* store, int kind, int B, int max_face, int max_edge, float bbox_scaled, const int* face_src,
+                    const int* edge_src, const int* rot, const double* scale, const bg_batch_out* out, bg_stream_t stream);
+
+/* utils.py:210-258 rotate_point_cloud as SurfData / EdgeData apply it (dataset.py:157-163, 204-211): x, out [M, P, 3] fp32, P <= 1024,
+ * one wave per item.  Item m is augmented iff aug && u > 0.5; then for the axes x, y, z in turn: subtract the mean point, rotate by the
+ * axis' quarter turn (a signed permutation), add the mean back, divide by the max-abs of the result -- all in fp64 (sums: per lane over
+ * its points p = lane, lane + 64, .. in order, then a butterfly across the wave; fixed by P alone), rounded to fp32 once at the end.
+ * Items that are not augmented are bitwise copies.  u [M] fp64 and turns [M, 3] int32 (device) replace the Philox draw: counter =
+ * (0, low 32 bits of g, draw_id, 0xDA7B0000 | bits 32..47 of g) with g = first_item + m, u and the turns from the four words as in
+ * the plan entry above.  M == 0 returns 0. */
+int bg_points_rotate_normalize(const float* x, long long M, int P, int aug, unsigned long long seed, unsigned draw_id,
+                               long long first_item, const double* u, const int* turns, float* out, bg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
