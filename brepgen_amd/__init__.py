@@ -9,6 +9,7 @@ Drop-in for the reference's call surface on that path only:
     compute_cov_mmd / jsd_between_point_cloud_sets   (metrics.py)   -> bg_chamfer_pairwise / bg_occupancy_counts
     sample_surface / sample_meshes                   (sample_points.py) -> bg_mesh_sample
     CADStore / augment_points (dataset.py: load_data, the six datasets) (dataset.py) -> bg_cad_filter / bg_batch_plan / bg_batch_gather
+    dedup_cads / unique_items (data_process/deduplicate_*.py)       (deduplicate.py) -> bg_points_sha256 / bg_digest_group_keys / bg_first_occurrence
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from .network import EdgePosNet, EdgeZNet, SurfPosNet, SurfZNet  # noqa: F401
@@ -34,6 +35,9 @@ __all__ += list(_FULL_VAE)
 # dataset.py's surface (dataset.py): the training batches of the six trainers, assembled on the device
 _DATASET = ("CADStore", "augment_points")
 __all__ += list(_DATASET)
+# data_process/deduplicate_cad.py and deduplicate_surfedge.py (deduplicate.py; `python -m brepgen_amd.deduplicate`)
+_DEDUPLICATE = ("point_digests", "cad_keys", "first_occurrence", "dedup_cads", "unique_items")
+__all__ += list(_DEDUPLICATE)
 
 
 def __getattr__(name):
@@ -49,4 +53,7 @@ def __getattr__(name):
     if name in _DATASET:
         from . import dataset
         return getattr(dataset, name)
+    if name in _DEDUPLICATE:
+        from . import deduplicate
+        return getattr(deduplicate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -158,6 +158,9 @@ _SIGNATURES = {
     "bg_batch_gather": (C.c_int, [C.POINTER(CadStore), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, fp,
                                   C.POINTER(BatchOut), vp]),
     "bg_points_rotate_normalize": (C.c_int, [fp, C.c_longlong, C.c_int, C.c_int, C.c_ulonglong, C.c_uint, C.c_longlong, fp, vp, fp, vp]),
+    "bg_points_sha256": (C.c_int, [fp, C.c_longlong, C.c_int, C.c_int, u8p, vp]),
+    "bg_digest_group_keys": (C.c_int, [u8p, vp, C.c_int, C.c_int, u8p, vp]),
+    "bg_first_occurrence": (C.c_int, [u8p, C.c_longlong, vp, C.c_longlong, u8p, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -135,6 +135,23 @@ class CADStore:
                                         stream()), "bg_cad_filter")
         return keep.bool()
 
+    def _unique_rows(self, grids, n, bit):
+        from . import deduplicate
+        if n == 0:
+            return torch.empty(0, dtype=torch.int64, device=self.device)
+        return deduplicate.first_occurrence(deduplicate.point_digests(grids[:n], bit)).nonzero().reshape(-1)
+
+    @torch.no_grad()
+    def unique_surfaces(self, bit=6):
+        """int64 [K] on the device, ascending: the rows of surf_ncs that deduplicate_surfedge.py keeps (first occurrence of every
+        `bit`-bit quantised grid; deduplicate.py), the store's pad row excluded.  Turning the mask into row numbers synchronises once."""
+        return self._unique_rows(self.surf_ncs, self._c.n_faces, bit)
+
+    @torch.no_grad()
+    def unique_edges(self, bit=6):
+        """int64 [K] on the device, ascending: the same for the rows of edge_ncs."""
+        return self._unique_rows(self.edge_ncs, self._c.n_edges, bit)
+
     def _indices(self, indices, max_face, max_edge):
         idx = _host(indices).astype(np.int64).reshape(-1)
         if idx.size and (idx.min() < 0 or idx.max() >= len(self)):

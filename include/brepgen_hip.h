@@ -678,6 +678,34 @@ int bg_batch_gather(const bg_cad_store* store, int kind, int B, int max_face, in
 int bg_points_rotate_normalize(const float* x, long long M, int P, int aug, unsigned long long seed, unsigned draw_id,
                                long long first_item, const double* u, const int* turns, float* out, bg_stream_t stream);
 
+/* ---- training-set de-duplication (data_process/deduplicate_cad.py, deduplicate_surfedge.py; csrc/hash_dedup.hip) ----
+ *
+ * digest[m] = sha256(real2bit(x[m], n_bits).reshape(-1, 3).tobytes()) for the M items x [M, P, 3] fp32, 1 <= P <= 1024 points each
+ * (1024: a surface grid, 32: an edge), 1 <= n_bits <= 16 (2^n - 1 is exact in fp32; the reference's default is 6).  Quantisation is
+ * convert_utils.real2bit step by step in fp32, one rounding each: t = x + 1; t = t * (2^n - 1); t = t / 2; clip to [0, 2^n - 1];
+ * truncate toward zero.  +-inf, -0.0 and values outside [-1, 1] follow from the clip; a NaN quantises to 0 (numpy's cast of a NaN is
+ * platform-defined).  The message is the 24 P bytes of the little-endian int64 values in memory order and is never materialised.
+ * digest [M, 32] uint8: the standard big-endian output bytes, so bytes(digest[m]).hex() is the reference's hexdigest.  Exactly
+ * [M, 32] bytes are written.  x 4-byte aligned (16-byte loads are used where P % 4 == 0 and x is 16-byte aligned), digest 16-byte
+ * aligned.  Sizes outside the limits: BG_E_SHAPE.  M == 0 returns 0. */
+int bg_points_sha256(const float* x, long long M, int P, int n_bits, uint8_t* digest, bg_stream_t stream);
+
+/* key[n] = sha256 of the concatenation of the digests off[n] .. off[n + 1] - 1 of digest [*, 32], sorted bytewise (equal digests
+ * stay as many as they are): hashlib.sha256(b''.join(sorted(d))).digest().  Equal keys <=> equal sorted digest lists <=> equal
+ * '_'-joined sorted hex strings of deduplicate_cad.py, up to SHA-256 collisions.  An empty group gives sha256(b'').  off [N + 1] int32
+ * ascending (device), max_group = the largest group as the host knows it, at most 4096 (more: BG_E_SHAPE, nothing is launched); a
+ * group that is longer after all is cut to max_group.  One workgroup per group, 32 max_group bytes of LDS.  digest and key 16-byte
+ * aligned.  N == 0 returns 0. */
+int bg_digest_group_keys(const uint8_t* digest, const int* off, int N, int max_group, uint8_t* key, bg_stream_t stream);
+
+/* keep[i] = 1 iff no j < i has key[j] == key[i] on all 32 bytes, else 0, for key [N, 32] uint8 (16-byte aligned), N <= 2^30 - 1.
+ * table [T] int32 is caller-owned workspace: T a power of two, T >= 2 N, T >= 2 (else BG_E_SHAPE); the entry fills it with -1 itself.
+ * It is an open-addressing table of item indices: the home slot of a key is its first 8 bytes read as a little-endian integer, masked
+ * to T - 1; probing is linear (slot + 1, wrapping).  Launch one claims a slot per distinct key (atomicCAS) and lowers its index
+ * (atomicMin); launch two looks every key up again.  The slot a key ends in may differ from run to run, keep does not.
+ * N == 0 returns 0. */
+int bg_first_occurrence(const uint8_t* key, long long N, int* table, long long T, uint8_t* keep, bg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
