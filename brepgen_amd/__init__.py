@@ -10,8 +10,10 @@ Drop-in for the reference's call surface on that path only:
     sample_surface / sample_meshes                   (sample_points.py) -> bg_mesh_sample
     CADStore / augment_points (dataset.py: load_data, the six datasets) (dataset.py) -> bg_cad_filter / bg_batch_plan / bg_batch_gather
     dedup_cads / unique_items (data_process/deduplicate_*.py)       (deduplicate.py) -> bg_points_sha256 / bg_digest_group_keys / bg_first_occurrence
+    optim.AdamW / optim.GradScaler / optim.clip_grad_norm_ (trainer.py's update) (optim.py) -> bg_mt_grad_stats / bg_mt_adamw_step / bg_optim_finish
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
+from . import optim  # noqa: F401
 from .network import EdgePosNet, EdgeZNet, SurfPosNet, SurfZNet  # noqa: F401
 from .schedulers import DDPMScheduler, PNDMScheduler  # noqa: F401
 from .utils import randn_tensor  # noqa: F401
@@ -20,7 +22,7 @@ from .vae import (AutoencoderKL1DFastDecode, AutoencoderKL1DFastEncode, Autoenco
 
 __all__ = ["SurfPosNet", "SurfZNet", "EdgePosNet", "EdgeZNet", "DDPMScheduler", "PNDMScheduler", "randn_tensor",
            "AutoencoderKLFastDecode", "AutoencoderKL1DFastDecode", "AutoencoderKLFastEncode",
-           "AutoencoderKL1DFastEncode"]
+           "AutoencoderKL1DFastEncode", "optim"]
 
 # pc_metric.py's surface (metrics.py), resolved on first use: `python -m brepgen_amd.metrics` must find the module not yet imported
 _METRICS = ("pairwise_chamfer", "compute_cov_mmd", "entropy_of_occupancy_grid", "jsd_between_point_cloud_sets",

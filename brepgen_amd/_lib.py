@@ -93,6 +93,24 @@ class BatchOut(C.Structure):         # bg_batch_out
                 ("vertex_pos", fp)]
 
 
+class MtRow(C.Structure):           # bg_mt_row
+    _fields_ = [("p", fp), ("g", fp), ("m", fp), ("v", fp), ("numel", C.c_longlong), ("lr", C.c_double), ("decay", C.c_float),
+                ("has_decay", C.c_int)]
+
+
+class MtChunk(C.Structure):         # bg_mt_chunk
+    _fields_ = [("first", C.c_longlong), ("tensor", C.c_int), ("_pad", C.c_int)]
+
+
+class OptimState(C.Structure):      # bg_optim_state
+    _fields_ = [("beta1_pow", C.c_double), ("beta2_pow", C.c_double), ("step", C.c_int), ("total_norm", C.c_float),
+                ("found_inf", C.c_int), ("_pad", C.c_int)]
+
+
+class ScalerState(C.Structure):     # bg_scaler_state
+    _fields_ = [("scale", C.c_float), ("growth_tracker", C.c_int)]
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("kernel", C.c_char_p), ("launches", C.c_int), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -161,6 +179,10 @@ _SIGNATURES = {
     "bg_points_sha256": (C.c_int, [fp, C.c_longlong, C.c_int, C.c_int, u8p, vp]),
     "bg_digest_group_keys": (C.c_int, [u8p, vp, C.c_int, C.c_int, u8p, vp]),
     "bg_first_occurrence": (C.c_int, [u8p, C.c_longlong, vp, C.c_longlong, u8p, vp]),
+    "bg_mt_grad_stats": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    "bg_mt_adamw_step": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_double, C.c_double, C.c_double, vp]),
+    "bg_optim_finish": (C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp]),
+    "bg_mt_scale_grads": (C.c_int, [vp, vp, C.c_int, vp, C.c_float, fp, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

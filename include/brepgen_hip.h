@@ -706,6 +706,63 @@ int bg_digest_group_keys(const uint8_t* digest, const int* off, int N, int max_g
  * N == 0 returns 0. */
 int bg_first_occurrence(const uint8_t* key, long long N, int* table, long long T, uint8_t* keep, bg_stream_t stream);
 
+/* ---- the update half of a trainer iteration (trainer.py: clip_grad_norm_, GradScaler.step / update, torch.optim.AdamW; csrc/optim.hip) ----
+ *
+ * Multi-tensor kernels over a device-resident table: one row per (param, grad, exp_avg, exp_avg_sq) quadruple of fp32, contiguous,
+ * 4-byte aligned tensors of numel elements each, and a chunk list that cuts every tensor into pieces of BG_OPTIM_CHUNK elements
+ * (the last one short; a tensor of 0 elements has none).  Launches use min(n_chunks, BG_OPTIM_MAX_BLOCKS) workgroups of 256 threads;
+ * workgroup b walks chunks b, b + grid, ...; inside a chunk thread t owns elements 4 (t + 256 j) .. + 3, j = 0 .. 3 -- a 16-byte
+ * access where every pointer of the chunk is 16-byte aligned, 4-byte accesses elsewhere.  Nothing here synchronises, allocates or uses
+ * atomics; every result is a function of the table, the chunk list and the data alone (bit-reproducible).  tests/optim_restate.py
+ * states the arithmetic in numpy. */
+#define BG_OPTIM_CHUNK 4096
+#define BG_OPTIM_MAX_BLOCKS 2048
+typedef struct bg_mt_row {
+    float* p; const float* g; float* m; float* v;   /* device; bg_mt_grad_stats / bg_mt_scale_grads read g (and numel) only */
+    long long numel;
+    double lr;                                      /* the group's learning rate, as the host holds it */
+    float decay;                                    /* float(1 - lr * weight_decay), formed in double on the host */
+    int has_decay;                                  /* 0: weight_decay == 0, the multiplication is skipped */
+} bg_mt_row;
+typedef struct bg_mt_chunk { long long first; int tensor; int _pad; } bg_mt_chunk;      /* elements first .. of row `tensor` */
+typedef struct bg_optim_state {                     /* device; all zero except the powers (1.0) before the first step */
+    double beta1_pow, beta2_pow;                    /* beta^step, one fp64 multiplication per successful step */
+    int step;                                       /* successful steps so far */
+    float total_norm;                               /* of the last finish */
+    int found_inf;                                  /* of the last finish */
+    int _pad;
+} bg_optim_state;
+typedef struct bg_scaler_state { float scale; int growth_tracker; } bg_scaler_state;      /* device; torch.amp.GradScaler's two tensors */
+
+/* Launch 1.  partials: BG_OPTIM_MAX_BLOCKS x 16 bytes of caller-owned device memory, 16-byte aligned; workgroup b writes entry b =
+ * (fp64 sum of double(g) * double(g) over its chunks, bits of the largest finite |g|, 1 if any g is inf or NaN).  Per thread the
+ * elements are added in the order chunk, j, element; then a 64-lane butterfly (xor 32, 16, .. 1), then ((w0 + w1) + w2) + w3 over
+ * the four waves.  n_chunks == 0 returns 0 and launches nothing. */
+int bg_mt_grad_stats(const bg_mt_row* table, const bg_mt_chunk* chunks, int n_chunks, void* partials, bg_stream_t stream);
+
+/* Launch 2.  Every workgroup sums the partials (lane l of one wave adds entries l, l + 64, .. in order, then the butterfly) and forms
+ *   total_norm = float(sqrt(sum));  c = max_norm >= 0 ? min(1, max_norm / (total_norm + 1e-6f)) : 1   (fp32; max_norm < 0: no clipping)
+ *   r = scaler ? float(1.0 / double(scaler->scale)) : 1;  found_inf = any non-finite g, or fl(fl(maxabs * c) * r) not finite.
+ * found_inf: returns, no byte of any p, m, v is written.  Otherwise per element, fp32, one rounding per operation, with
+ * bc_i = 1 - state->beta_i_pow * beta_i (fp64):
+ *   g' = (g * c) * r;  p = p * decay (has_decay only);  m = m + (g' - m) * float(1 - beta1);  v = v * float(beta2) + float(1 - beta2) * (g' * g');
+ *   denom = sqrt(v) / float(sqrt(bc2)) + float(eps);  p = p - float(lr / bc1) * (m / denom).
+ * g is read only; state and scaler are read only (bg_optim_finish advances them).  scaler may be NULL. */
+int bg_mt_adamw_step(const bg_mt_row* table, const bg_mt_chunk* chunks, int n_chunks, const void* partials, const bg_optim_state* state,
+                     const bg_scaler_state* scaler, float max_norm, double beta1, double beta2, double eps, bg_stream_t stream);
+
+/* Launch 3, one wave.  Derives total_norm and found_inf as launch 2 did (same max_norm, same scaler state) and publishes them in
+ * state.  found_inf: scale *= backoff_factor, growth_tracker = 0.  Otherwise step += 1 and beta_i_pow *= beta_i (n_chunks > 0 only), growth_tracker += 1, and
+ * at growth_tracker == growth_interval: scale *= growth_factor if that is finite, growth_tracker = 0 (torch's _amp_update_scale_).
+ * scaler may be NULL (the factors are ignored). */
+int bg_optim_finish(const void* partials, int n_chunks, bg_optim_state* state, bg_scaler_state* scaler, float max_norm, double beta1,
+                    double beta2, double growth_factor, double backoff_factor, int growth_interval, bg_stream_t stream);
+
+/* g = g * c in place with c of launch 2 (max_norm >= 0) from the partials of a bg_mt_grad_stats over the same lists: the stand-alone
+ * clip_grad_norm_.  norm_out (device fp32, may be NULL) receives total_norm; n_chunks == 0 writes 0 there. */
+int bg_mt_scale_grads(const bg_mt_row* table, const bg_mt_chunk* chunks, int n_chunks, const void* partials, float max_norm,
+                      float* norm_out, bg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
