@@ -11,8 +11,12 @@ attention = one fused q|k|v GEMM + ``bg_small_attn`` + projection GEMM; ``Upsamp
 The nn.Module tree below only holds parameters.  Like the denoisers, bf16 operands inside autocast, exact fp32 outside.
 
 A pass is ONE C call: each module compiles itself (once per dtype) into a flat ``bg_vae_op`` program and ``bg_vae_run``
-enqueues every launch of it, chunking the batch against a caller-owned workspace.  (A step-by-step Python driver of the same
-primitives -- the round-1 path -- is kept as a cross-check in tests/vae_stepwise.py, outside the product module.)
+enqueues every launch of it, chunking the batch against a caller-owned workspace.
+
+Each network's layer order is written once, in its class's ``_program(pg, P)``: a walk that names sub-modules and calls the primitives
+of its executor ``pg`` (``conv``, ``norm_act_add``, ``attn``, ``resample1d``, ``free``; the two residual blocks are compositions of them in
+``_Blocks``).  ``_Program`` records the calls as program steps; ``P`` (``_pack(dt)``) packs a sub-module's weights the first time the walk
+names it.  The second executor, tests/vae_stepwise.py, runs every primitive at once from Python -- the cross-check of ``bg_vae_run``.
 
 Below the decoders: the Fast encoders (posterior mean only), and the full ``AutoencoderKL`` / ``AutoencoderKL1D`` the VAE trainers build
 (trainer.py:20-30, 150-160), which run the same two programs with one ``bg_vae_posterior`` launch (``DiagonalGaussianDistribution``:
@@ -164,8 +168,41 @@ VOP_CONV, VOP_NORM_ACT_ADD, VOP_ATTN, VOP_UP1D, VOP_DOWN1D = 0, 1, 2, 3, 4
 VAE_OUT = 255
 
 
-class _Program:
+def _check(t, what):
+    if not t.is_cuda:
+        raise _lib.BrepgenHipError(f"brepgen_amd VAE {what} runs on the MI355X only (tensor on {t.device})")
+
+
+class _Blocks:
+    """The residual blocks of the four networks, written once over the primitives of whoever executes a walk (`_program`): `_Program`
+    below records each as a bg_vae_op step, tests/vae_stepwise.py runs each at once.  A walk names modules; their weights come
+    from `packs`, the `_Packs` the walk was given."""
+    PRIMITIVES = ("conv", "norm_act_add", "attn", "resample1d", "free")
+    packs = None
+
+    def resnet2d(self, x, r):                          # diffusers ResnetBlock2D
+        h = self.conv(x, r.conv1, 3, 3, norm=r.norm1, act=ACT_SILU)
+        sc = self.conv(x, r.conv_shortcut, 1, 1) if hasattr(r, "conv_shortcut") else x
+        out = self.conv(h, r.conv2, 3, 3, norm=r.norm2, act=ACT_SILU, res=sc)
+        self.free(h, x, sc)
+        return out
+
+    def resconv(self, x, r):
+        # diffusers ResConvBlock: conv k5 -> GroupNorm(1) -> GELU -> conv k5 -> GroupNorm(1) -> GELU, + (1x1) skip.  group_norm_1 + GELU
+        # fold into the gather of conv_2; the trailing group_norm_2 + GELU cannot fold into the next consumer (the residual add sits in
+        # between), so it is one pass of its own with the add fused.
+        h1 = self.conv(x, r.conv_1, 1, 5)
+        h2 = self.conv(h1, r.conv_2, 1, 5, norm=r.group_norm_1, act=ACT_GELU)
+        self.free(h1)
+        sk = self.conv(x, r.conv_skip, 1, 1) if hasattr(r, "conv_skip") else x
+        out = self.norm_act_add(h2, r.group_norm_2, ACT_GELU, sk)
+        self.free(h2, x, sk)
+        return out
+
+
+class _Program(_Blocks):
     """A flat bg_vae_op program under construction: steps + a free-list slot allocator (slot 0 = the input)."""
+    input = 0
 
     def __init__(self):
         self.steps, self.keep, self._free, self.n_slots = [], [], [], 1
@@ -180,9 +217,9 @@ class _Program:
     def free(self, *slots):
         self._free.extend(s for s in dict.fromkeys(slots) if s > 0 and s not in self._free)
 
-    def step(self, op, src, dst, res=-1):
+    def step(self, op, src, dst, res=None):
         o = _lib.VaeOp()
-        o.op, o.src, o.res = op, src, res
+        o.op, o.src, o.res = op, src, -1 if res is None else res
         o.dst = self.new() if dst is None else dst
         o.stride = 1
         self.steps.append(o)
@@ -193,7 +230,8 @@ class _Program:
         self.keep += [g, b]
         o.gn_gamma, o.gn_beta, o.gn_groups, o.gn_eps, o.act = ptr(g), ptr(b), norm.num_groups, norm.eps, act
 
-    def conv(self, src, pk, kh, kw, up=0, norm=None, act=ACT_NONE, res=-1, stride=1, pad_mode=0, dst=None, n_out=None):
+    def conv(self, src, conv, kh, kw, up=0, norm=None, act=ACT_NONE, res=None, stride=1, pad_mode=0, dst=None, n_out=None, pad16=64):
+        pk = self.packs.conv(conv, pad16)
         o = self.step(VOP_CONV, src, dst, res)
         o.kh, o.kw, o.up, o.stride, o.pad_mode = kh, kw, up, stride, pad_mode
         o.n_out, o.n_pad, o.w_dtype = pk.n if n_out is None else n_out, pk.w.shape[0], _CODE[pk.dtype]
@@ -202,30 +240,19 @@ class _Program:
             self.norm(o, norm, act)
         return o.dst
 
-    def attn(self, src, qkv, proj, norm, heads, scale):
+    def norm_act_add(self, src, norm, act, res):
+        o = self.step(VOP_NORM_ACT_ADD, src, None, res)
+        self.norm(o, norm, act)
+        return o.dst
+
+    def attn(self, src, at, heads, scale):
+        qkv, proj = self.packs.attn(at)
         o = self.step(VOP_ATTN, src, None)
         o.n_pad, o.w_dtype, o.w, o.bias = qkv.w.shape[0], _CODE[qkv.dtype], ptr(qkv.w), ptr(qkv.b)
         o.n_pad2, o.w2_dtype, o.w2, o.bias2 = proj.w.shape[0], _CODE[proj.dtype], ptr(proj.w), ptr(proj.b)
         o.heads, o.scale = heads, scale
-        self.norm(o, norm, ACT_NONE)
+        self.norm(o, at.group_norm, ACT_NONE)
         self.free(src)
-        return o.dst
-
-    def resnet2d(self, x, P, name, r):                 # diffusers ResnetBlock2D
-        h = self.conv(x, P[name + "c1"], 3, 3, norm=r.norm1, act=ACT_SILU)
-        sc = self.conv(x, P[name + "sc"], 1, 1) if name + "sc" in P else x
-        out = self.conv(h, P[name + "c2"], 3, 3, norm=r.norm2, act=ACT_SILU, res=sc)
-        self.free(h, x, sc)
-        return out
-
-    def resconv(self, x, P, name, r):                  # diffusers ResConvBlock (see _HipVAE._resconv)
-        h1 = self.conv(x, P[name + "c1"], 1, 5)
-        h2 = self.conv(h1, P[name + "c2"], 1, 5, norm=r.group_norm_1, act=ACT_GELU)
-        self.free(h1)
-        sk = self.conv(x, P[name + "sk"], 1, 1) if name + "sk" in P else x
-        o = self.step(VOP_NORM_ACT_ADD, h2, None, sk)
-        self.norm(o, r.group_norm_2, ACT_GELU)
-        self.free(h2, x, sk)
         return o.dst
 
     def resample1d(self, x, op):
@@ -339,6 +366,13 @@ class _HipVAE(nn.Module):
         return torch.float32
 
     # ---- packing ----
+    def _pack(self, dt):
+        """The module's weights in compute dtype `dt`, packed as a walk asks for them; kept (with the programs that point into them) until
+        the parameters move or change."""
+        if dt not in self._packs:
+            self._packs[dt] = _Packs(dt)
+        return self._packs[dt]
+
     @staticmethod
     def _pack_gemm(weight2d, bias, dt, pad16=64):
         n, k = weight2d.shape
@@ -355,7 +389,8 @@ class _HipVAE(nn.Module):
         p.b, p.n, p.k, p.dtype = b.contiguous(), n, k, use
         return p
 
-    def _pack_conv(self, conv, dt, pad16=64):
+    @staticmethod
+    def _pack_conv(conv, dt, pad16=64):
         """pad16: rows the 16-bit weight matrix is zero-padded to a multiple of.  128 for a NARROW windowed convolution (conv_out:
         3 output channels): the implicit GEMM then takes it as one 128-column tile that stores only the real columns, instead of
         materialising the 9-fold / 3-fold im2col matrix of the largest activation of the pass for the generic kernel."""
@@ -364,28 +399,30 @@ class _HipVAE(nn.Module):
             w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)
         else:                                          # Conv2d [Cout, Cin, kh, kw] -> [Cout, kh*kw*Cin]
             w2 = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
-        return self._pack_gemm(w2, conv.bias, dt, pad16)
+        return _HipVAE._pack_gemm(w2, conv.bias, dt, pad16)
 
-    # ---- primitive steps on channels-last fp32 tensors [S, H, W, C] ----
-    def _pack_resnet2d(self, P, name, r, dt):
-        P[name + "c1"], P[name + "c2"] = self._pack_conv(r.conv1, dt), self._pack_conv(r.conv2, dt)
-        if hasattr(r, "conv_shortcut"):
-            P[name + "sc"] = self._pack_conv(r.conv_shortcut, dt)
 
-    def _pack_attn2d(self, P, key, at, dt):
-        P[key + "qkv"] = self._pack_gemm(torch.cat([at.to_q.weight, at.to_k.weight, at.to_v.weight]),
-                                         torch.cat([at.to_q.bias, at.to_k.bias, at.to_v.bias]), dt)
-        P[key + "proj"] = self._pack_gemm(at.to_out[0].weight, at.to_out[0].bias, dt)
+class _Packs(dict):
+    """One module's pack cache for one compute dtype: sub-module -> what `_pack_conv` / `_pack_gemm` made of it, packed the first time a
+    walk names the sub-module."""
 
-    def _pack_resconv(self, P, name, r, dt):
-        P[name + "c1"], P[name + "c2"] = self._pack_conv(r.conv_1, dt), self._pack_conv(r.conv_2, dt)
-        if hasattr(r, "conv_skip"):
-            P[name + "sk"] = self._pack_conv(r.conv_skip, dt)
+    def __init__(self, dt):
+        super().__init__()
+        self.dt = dt
 
-    def _pack_attn1d(self, P, key, at, dt):
-        P[key + "qkv"] = self._pack_gemm(torch.cat([at.query.weight, at.key.weight, at.value.weight]),
-                                         torch.cat([at.query.bias, at.key.bias, at.value.bias]), dt)
-        P[key + "proj"] = self._pack_gemm(at.proj_attn.weight, at.proj_attn.bias, dt)
+    def conv(self, conv, pad16=64):
+        if conv not in self:
+            self[conv] = _HipVAE._pack_conv(conv, self.dt, pad16)
+        return self[conv]
+
+    def attn(self, at):
+        """-> (fused q|k|v, output projection) of a diffusers Attention (2-D mid block) or AttentionBlock (1-D mid block)."""
+        if at not in self:
+            q, k, v, proj = (at.to_q, at.to_k, at.to_v, at.to_out[0]) if hasattr(at, "to_q") else (at.query, at.key, at.value, at.proj_attn)
+            self[at] = (_HipVAE._pack_gemm(torch.cat([q.weight, k.weight, v.weight]), torch.cat([q.bias, k.bias, v.bias]), self.dt),
+                        _HipVAE._pack_gemm(proj.weight, proj.bias, self.dt))
+        return self[at]
+
 
 class AutoencoderKLFastDecode(_HipVAE):
     """Surface-VAE decoder: z [F,3,4,4] -> points [F,3,32,32]  (network.py:948-1040)."""
@@ -401,53 +438,32 @@ class AutoencoderKLFastDecode(_HipVAE):
         self.decoder = _Decoder2D(latent_channels, out_channels, self.block_out, layers_per_block, norm_num_groups)
         self.post_quant_conv = nn.Conv2d(latent_channels, latent_channels, 1)
 
-    def _pack(self, dt):
-        if dt in self._packs:
-            return self._packs[dt]
-        P = {}
-        d = self.decoder
-        P["pq"] = self._pack_conv(self.post_quant_conv, dt)
-        P["in"] = self._pack_conv(d.conv_in, dt)
-        self._pack_resnet2d(P, "m0", d.mid_block.resnets[0], dt)
-        self._pack_resnet2d(P, "m1", d.mid_block.resnets[1], dt)
-        self._pack_attn2d(P, "ma", d.mid_block.attentions[0], dt)
-        for bi, blk in enumerate(d.up_blocks):
-            for ri, r in enumerate(blk.resnets):
-                self._pack_resnet2d(P, f"u{bi}r{ri}", r, dt)
-            if hasattr(blk, "upsamplers"):
-                P[f"u{bi}up"] = self._pack_conv(blk.upsamplers[0].conv, dt)
-        P["out"] = self._pack_conv(d.conv_out, dt, pad16=128)
-        self._packs[dt] = P
-        return P
-
     def _program(self, pg, P):
-        d = self.decoder
-        x = pg.conv(0, P["pq"], 1, 1)
-        x2 = pg.conv(x, P["in"], 3, 3)
+        pg.packs, d = P, self.decoder
+        x = pg.conv(pg.input, self.post_quant_conv, 1, 1)
+        x2 = pg.conv(x, d.conv_in, 3, 3)
         pg.free(x)
-        x = pg.resnet2d(x2, P, "m0", d.mid_block.resnets[0])
-        x = pg.attn(x, P["maqkv"], P["maproj"], d.mid_block.attentions[0].group_norm, 1, 1.0 / math.sqrt(self.block_out[-1]))
-        x = pg.resnet2d(x, P, "m1", d.mid_block.resnets[1])
-        for bi, blk in enumerate(d.up_blocks):
-            for ri, r in enumerate(blk.resnets):
-                x = pg.resnet2d(x, P, f"u{bi}r{ri}", r)
+        x = pg.resnet2d(x2, d.mid_block.resnets[0])
+        x = pg.attn(x, d.mid_block.attentions[0], 1, 1.0 / math.sqrt(self.block_out[-1]))
+        x = pg.resnet2d(x, d.mid_block.resnets[1])
+        for blk in d.up_blocks:
+            for r in blk.resnets:
+                x = pg.resnet2d(x, r)
             if hasattr(blk, "upsamplers"):
-                x2 = pg.conv(x, P[f"u{bi}up"], 3, 3, up=1)
+                x2 = pg.conv(x, blk.upsamplers[0].conv, 3, 3, up=1)
                 pg.free(x)
                 x = x2
-        pg.conv(x, P["out"], 3, 3, norm=d.conv_norm_out, act=ACT_SILU, dst=VAE_OUT)
+        pg.conv(x, d.conv_out, 3, 3, norm=d.conv_norm_out, act=ACT_SILU, dst=VAE_OUT, pad16=128)
         return pg
 
     def forward(self, z, return_dict=True, generator=None):
-        if not z.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE decode runs on the MI355X only (tensor on {z.device})")
+        _check(z, "decode")
         z_cl = z.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
         return self._decode_cl(z_cl).permute(0, 3, 1, 2).contiguous()
 
     def _decode_cl(self, z_cl):
         """Channels-last latents [F,4,4,3] -> channels-last point grids [F,32,32,3] (the layout the kernels use)."""
         dt = self._dtype()
-        n = z_cl.shape[0]
         side = z_cl.shape[1] * 2 ** (len(self.block_out) - 1)
         return self._run(z_cl, (side, side, self.out_ch), dt)
 
@@ -456,8 +472,7 @@ class AutoencoderKLFastDecode(_HipVAE):
         [..., 32, 32, 3].  Equals sample.py:289-290's `vae(z.unflatten(-1,(16,3)).flatten(0,1).permute(0,2,1)
         .unflatten(-1,(4,4))).permute(0,2,3,1).unflatten(0,(B,S))` without the two NCHW round trips: the token
         layout already is the channels-last layout."""
-        if not surfZ.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE decode runs on the MI355X only (tensor on {surfZ.device})")
+        _check(surfZ, "decode")
         lead = surfZ.shape[:-1]
         if surfZ.numel() == 0:                                       # a rank that owns no sample of a sharded batch
             return surfZ.new_zeros((*lead, *self._decode_cl_shape()), dtype=torch.float32)
@@ -481,58 +496,38 @@ class AutoencoderKL1DFastDecode(_HipVAE):
         self.decoder = _Decoder1D(latent_channels, out_channels, self.block_out, norm_num_groups)
         self.post_quant_conv = nn.Conv1d(latent_channels, latent_channels, 1)
 
-    def _pack(self, dt):
-        if dt in self._packs:
-            return self._packs[dt]
-        P = {}
-        d = self.decoder
-        P["pq"] = self._pack_conv(self.post_quant_conv, dt)
-        P["in"] = self._pack_conv(d.conv_in, dt)
-        for i in range(6):
-            self._pack_resconv(P, f"m{i}", d.mid_block.resnets[i], dt)
-            self._pack_attn1d(P, f"a{i}", d.mid_block.attentions[i], dt)
-        for bi, blk in enumerate(d.up_blocks):
-            for ri, r in enumerate(blk.resnets):
-                self._pack_resconv(P, f"u{bi}r{ri}", r, dt)
-        P["out"] = self._pack_conv(d.conv_out, dt, pad16=128)
-        self._packs[dt] = P
-        return P
-
     def _program(self, pg, P):
-        d = self.decoder
-        x = pg.conv(0, P["pq"], 1, 1)
-        x2 = pg.conv(x, P["in"], 1, 3)
+        pg.packs, d = P, self.decoder
+        x = pg.conv(pg.input, self.post_quant_conv, 1, 1)
+        x2 = pg.conv(x, d.conv_in, 1, 3)
         pg.free(x)
         x = x2
         c = self.block_out[-1]
-        for i in range(6):
-            x = pg.resconv(x, P, f"m{i}", d.mid_block.resnets[i])
-            x = pg.attn(x, P[f"a{i}qkv"], P[f"a{i}proj"], d.mid_block.attentions[i].group_norm, c // 32, 1.0 / math.sqrt(32))
-        for bi, blk in enumerate(d.up_blocks):
-            for ri, r in enumerate(blk.resnets):
-                x = pg.resconv(x, P, f"u{bi}r{ri}", r)
+        for r, at in zip(d.mid_block.resnets, d.mid_block.attentions):
+            x = pg.resconv(x, r)
+            x = pg.attn(x, at, c // 32, 1.0 / math.sqrt(32))
+        for blk in d.up_blocks:
+            for r in blk.resnets:
+                x = pg.resconv(x, r)
             x = pg.resample1d(x, VOP_UP1D)
-        pg.conv(x, P["out"], 1, 3, norm=d.conv_norm_out, act=ACT_SILU, dst=VAE_OUT)
+        pg.conv(x, d.conv_out, 1, 3, norm=d.conv_norm_out, act=ACT_SILU, dst=VAE_OUT, pad16=128)
         return pg
 
     def forward(self, z, return_dict=True):
-        if not z.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE decode runs on the MI355X only (tensor on {z.device})")
+        _check(z, "decode")
         z_cl = z.detach().to(torch.float32).permute(0, 2, 1).contiguous()          # [G, L, 3]
         return self._decode_cl(z_cl).permute(0, 2, 1).contiguous()
 
     def _decode_cl(self, z_cl):
         """Channels-last latents [G,4,3] -> channels-last polylines [G,32,3]."""
         dt = self._dtype()
-        n = z_cl.shape[0]
         length = z_cl.shape[1] * 2 ** len(self.block_out)
         return self._run(z_cl, (length, self.out_ch), dt)
 
     def decode_tokens(self, edgeZ):
         """Token-layout latents [..., 4*3] (the first 12 of EdgeZNet's 18 channels) -> polylines [..., 32, 3]; equals
         sample.py:293-294's `vae(z.unflatten(-1,(4,3)).reshape(-1,4,3).permute(0,2,1)).permute(0,2,1).reshape(B,S,E,32,3)`."""
-        if not edgeZ.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE decode runs on the MI355X only (tensor on {edgeZ.device})")
+        _check(edgeZ, "decode")
         lead = edgeZ.shape[:-1]
         if edgeZ.numel() == 0:
             return edgeZ.new_zeros((*lead, 4 * 2 ** len(self.block_out), self.out_ch), dtype=torch.float32)
@@ -611,61 +606,40 @@ class AutoencoderKLFastEncode(_HipVAE):
         self.encoder = _Encoder2D(in_channels, latent_channels, self.block_out, layers_per_block, norm_num_groups)
         self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
 
-    def _pack(self, dt):
-        if dt in self._packs:
-            return self._packs[dt]
-        P, e = {}, self.encoder
-        P["in"] = self._pack_conv(e.conv_in, dt)
-        for bi, blk in enumerate(e.down_blocks):
-            for ri, r in enumerate(blk.resnets):
-                self._pack_resnet2d(P, f"d{bi}r{ri}", r, dt)
-            if hasattr(blk, "downsamplers"):
-                P[f"d{bi}dn"] = self._pack_conv(blk.downsamplers[0].conv, dt)
-        self._pack_resnet2d(P, "m0", e.mid_block.resnets[0], dt)
-        self._pack_resnet2d(P, "m1", e.mid_block.resnets[1], dt)
-        self._pack_attn2d(P, "ma", e.mid_block.attentions[0], dt)
-        P["out"] = self._pack_conv(e.conv_out, dt, pad16=128)
-        P["q"] = self._pack_conv(self.quant_conv, dt)
-        self._packs[dt] = P
-        return P
-
     def _program(self, pg, P):
-        e = self.encoder
-        x = pg.conv(0, P["in"], 3, 3)
-        for bi, blk in enumerate(e.down_blocks):
-            for ri, r in enumerate(blk.resnets):
-                x = pg.resnet2d(x, P, f"d{bi}r{ri}", r)
-            if hasattr(blk, "downsamplers"):
-                x2 = pg.conv(x, P[f"d{bi}dn"], 3, 3, stride=2, pad_mode=1)
+        pg.packs, e = P, self.encoder
+        x = pg.conv(pg.input, e.conv_in, 3, 3)
+        for blk in e.down_blocks:
+            for r in blk.resnets:
+                x = pg.resnet2d(x, r)
+            if hasattr(blk, "downsamplers"):                  # Downsample2D: pad (0,1,0,1), conv 3x3 stride 2
+                x2 = pg.conv(x, blk.downsamplers[0].conv, 3, 3, stride=2, pad_mode=1)
                 pg.free(x)
                 x = x2
-        x = pg.resnet2d(x, P, "m0", e.mid_block.resnets[0])
-        x = pg.attn(x, P["maqkv"], P["maproj"], e.mid_block.attentions[0].group_norm, 1, 1.0 / math.sqrt(self.block_out[-1]))
-        x = pg.resnet2d(x, P, "m1", e.mid_block.resnets[1])
-        x2 = pg.conv(x, P["out"], 3, 3, norm=e.conv_norm_out, act=ACT_SILU)
+        x = pg.resnet2d(x, e.mid_block.resnets[0])
+        x = pg.attn(x, e.mid_block.attentions[0], 1, 1.0 / math.sqrt(self.block_out[-1]))
+        x = pg.resnet2d(x, e.mid_block.resnets[1])
+        x2 = pg.conv(x, e.conv_out, 3, 3, norm=e.conv_norm_out, act=ACT_SILU, pad16=128)
         pg.free(x)
-        pg.conv(x2, P["q"], 1, 1, dst=VAE_OUT, n_out=self.n_out)        # n_out = latent: DiagonalGaussianDistribution(moments).mode() = mean
+        pg.conv(x2, self.quant_conv, 1, 1, dst=VAE_OUT, n_out=self.n_out)   # n_out = latent: DiagonalGaussianDistribution(moments).mode() = mean
         return pg
 
     def forward(self, x, return_dict=True):
-        if not x.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE encode runs on the MI355X only (tensor on {x.device})")
+        _check(x, "encode")
         x_cl = x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
         return self._encode_cl(x_cl).permute(0, 3, 1, 2).contiguous()
 
     def _encode_cl(self, x_cl):
         """Channels-last point grids [F,32,32,3] -> channels-last latent modes [F,4,4,3]."""
         dt = self._dtype()
-        n, side = x_cl.shape[0], x_cl.shape[1]
-        lat = side >> (len(self.block_out) - 1)
+        lat = x_cl.shape[1] >> (len(self.block_out) - 1)
         return self._run(x_cl, (lat, lat, self.n_out), dt)
 
     def encode_tokens(self, surfPnt):
         """Point grids [..., 32, 32, 3] (the datasets' layout) -> token-layout latents [..., 48]; equals trainer.py:519-524
         `vae(p.flatten(0,1).permute(0,3,1,2)).unflatten(0,(B,-1)).flatten(-2,-1).permute(0,1,3,2).flatten(-2,-1)` without
         the NCHW round trips."""
-        if not surfPnt.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE encode runs on the MI355X only (tensor on {surfPnt.device})")
+        _check(surfPnt, "encode")
         lead = surfPnt.shape[:-3]
         x_cl = surfPnt.detach().to(torch.float32).reshape(-1, *surfPnt.shape[-3:]).contiguous()
         z = self._encode_cl(x_cl)                                  # [F, 4, 4, latent]
@@ -684,55 +658,36 @@ class AutoencoderKL1DFastEncode(_HipVAE):
         self.encoder = _Encoder1D(in_channels, latent_channels, self.block_out, norm_num_groups)
         self.quant_conv = nn.Conv1d(2 * latent_channels, 2 * latent_channels, 1)
 
-    def _pack(self, dt):
-        if dt in self._packs:
-            return self._packs[dt]
-        P, e = {}, self.encoder
-        P["in"] = self._pack_conv(e.conv_in, dt)
-        for bi, blk in enumerate(e.down_blocks):
-            for ri, r in enumerate(blk.resnets):
-                self._pack_resconv(P, f"d{bi}r{ri}", r, dt)
-        for i in range(6):
-            self._pack_resconv(P, f"m{i}", e.mid_block.resnets[i], dt)
-            self._pack_attn1d(P, f"a{i}", e.mid_block.attentions[i], dt)
-        P["out"] = self._pack_conv(e.conv_out, dt, pad16=128)
-        P["q"] = self._pack_conv(self.quant_conv, dt)
-        self._packs[dt] = P
-        return P
-
     def _program(self, pg, P):
-        e = self.encoder
-        x = pg.conv(0, P["in"], 1, 3)
-        for bi, blk in enumerate(e.down_blocks):
+        pg.packs, e = P, self.encoder
+        x = pg.conv(pg.input, e.conv_in, 1, 3)
+        for blk in e.down_blocks:
             x = pg.resample1d(x, VOP_DOWN1D)
-            for ri, r in enumerate(blk.resnets):
-                x = pg.resconv(x, P, f"d{bi}r{ri}", r)
+            for r in blk.resnets:
+                x = pg.resconv(x, r)
         c = self.block_out[-1]
-        for i in range(6):
-            x = pg.resconv(x, P, f"m{i}", e.mid_block.resnets[i])
-            x = pg.attn(x, P[f"a{i}qkv"], P[f"a{i}proj"], e.mid_block.attentions[i].group_norm, c // 32, 1.0 / math.sqrt(32))
-        x2 = pg.conv(x, P["out"], 1, 3, norm=e.conv_norm_out, act=ACT_SILU)
+        for r, at in zip(e.mid_block.resnets, e.mid_block.attentions):
+            x = pg.resconv(x, r)
+            x = pg.attn(x, at, c // 32, 1.0 / math.sqrt(32))
+        x2 = pg.conv(x, e.conv_out, 1, 3, norm=e.conv_norm_out, act=ACT_SILU, pad16=128)
         pg.free(x)
-        pg.conv(x2, P["q"], 1, 1, dst=VAE_OUT, n_out=self.n_out)
+        pg.conv(x2, self.quant_conv, 1, 1, dst=VAE_OUT, n_out=self.n_out)
         return pg
 
     def forward(self, sample, sample_posterior=False, return_dict=True, generator=None):
-        if not sample.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE encode runs on the MI355X only (tensor on {sample.device})")
+        _check(sample, "encode")
         x_cl = sample.detach().to(torch.float32).permute(0, 2, 1).contiguous()
         return self._encode_cl(x_cl).permute(0, 2, 1).contiguous()
 
     def _encode_cl(self, x_cl):
         """Channels-last polylines [G,32,3] -> channels-last latent modes [G,4,3]."""
         dt = self._dtype()
-        n = x_cl.shape[0]
         return self._run(x_cl, (x_cl.shape[1] >> len(self.block_out), self.n_out), dt)
 
     def encode_tokens(self, edgePnt):
         """Polylines [..., 32, 3] -> token-layout latents [..., 12]; equals trainer.py:924-929
         `vae(p.flatten(0,1).flatten(0,1).permute(0,2,1)) ... .permute(0,1,2,4,3).flatten(-2,-1)`."""
-        if not edgePnt.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE encode runs on the MI355X only (tensor on {edgePnt.device})")
+        _check(edgePnt, "encode")
         lead = edgePnt.shape[:-2]
         x_cl = edgePnt.detach().to(torch.float32).reshape(-1, *edgePnt.shape[-2:]).contiguous()
         z = self._encode_cl(x_cl)                                  # [G, 4, latent]
@@ -898,14 +853,10 @@ class _FullVAE(nn.Module):
     # switches of _HipVAE, set on both runners
     compute_dtype, WS_BUDGET, two_streams = _on_runners("compute_dtype"), _on_runners("WS_BUDGET"), _on_runners("two_streams")
 
-    def _check(self, t, what):
-        if not t.is_cuda:
-            raise _lib.BrepgenHipError(f"brepgen_amd VAE {what} runs on the MI355X only (tensor on {t.device})")
-
     def _points_cl(self, x):
         """Points in the datasets' layout [..., (32,) 32, 3] or the trainers' permuted [n, 3, (32,) 32] -> (channels-last [N, (32,) 32, 3],
         restore), restore(y_cl) giving y in x's layout.  The last dimension decides: in_channels long = the datasets' layout."""
-        self._check(x, "encode")
+        _check(x, "encode")
         rank = self._RANK
         x = x.detach().to(torch.float32)
         if x.shape[-1] == self.in_ch and x.dim() >= rank + 1:
@@ -922,19 +873,19 @@ class _FullVAE(nn.Module):
         return self._runners[1]._decode_cl(z_cl)
 
     def encode(self, x, return_dict=True):
-        self._check(x, "encode")
+        _check(x, "encode")
         posterior = self._encode_cl(_to_cl(x.detach().to(torch.float32)))
         return AutoencoderKLOutput(posterior) if return_dict else (posterior,)
 
     def decode(self, z, return_dict=True):
-        self._check(z, "decode")
+        _check(z, "decode")
         dec = _to_ref(self._decode_cl(_to_cl(z.detach().to(torch.float32))))
         return DecoderOutput(dec) if return_dict else (dec,)
 
     def forward(self, sample, sample_posterior=False, return_dict=True, generator=None, *, noise=None):
         """network.py:660-687: encode, sample the posterior (or take its mode), decode -- the encode program, one bg_vae_posterior and the
         decode program on the current stream, channels-last in between."""
-        self._check(sample, "forward")
+        _check(sample, "forward")
         posterior = self._encode_cl(_to_cl(sample.detach().to(torch.float32)))
         if sample_posterior:
             z_cl = posterior._sample_cl(generator, noise)

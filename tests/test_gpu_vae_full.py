@@ -177,6 +177,22 @@ def test_full_vae_equals_the_fast_classes_bit_for_bit(pc, kind, dt):
         assert not torch.equal(z, dist.mode()) and torch.equal(dist.logvar, torch.clamp(dist.parameters[:, 3:], -30.0, 20.0))
 
 
+@pytest.mark.parametrize("dt", [F32, BF16])
+@pytest.mark.parametrize("kind,n", [("surf", 20), ("edge", 96)])
+def test_full_vae_encode_program_equals_step_by_step(pc, kind, n, dt):
+    """The widened encoder (all 2 * latent moments) through bg_vae_run and through the step-by-step driver of the same walk: the same bits
+    (the batch sizes of test_gpu_round2.py::test_vae_program_equals_step_by_step)."""
+    from vae_stepwise import stepwise
+    c = case(pc, kind)
+    _set_dtype(c, dt)
+    enc = c["full"]._runners[0]
+    x = torch.randn(n, *c["x"].shape[1:], generator=pc.gen(300 + n)).cuda()
+    with torch.no_grad():
+        a = c["full"].encode(x).latent_dist.parameters
+        b = stepwise(enc, x)
+    assert a.shape == b.shape == (n, 6, *c["mom"].shape[2:]) and torch.isfinite(a).all() and torch.equal(a, b)
+
+
 # (max abs, mean abs) error of the fp32 chain encode -> sample(noise) -> decode against the oracle's own chain (|ref|max 3.08 / 2.00), and
 # the relative error of vae_loss's (mse, kl) against the oracle chain's values (mse 1.361 / 1.873, kl 12.49 / 7.741): measured once on the
 # MI355X with these seeds (every run prints its figures) and asserted at 2x, the convention of test_vae_decode_bf16.  The chain is

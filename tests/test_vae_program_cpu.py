@@ -48,3 +48,34 @@ def test_malformed_programs_are_refused():
     bad = (_lib.VaeOp * n)(*pg.steps)
     bad[2].op = 17
     assert lib.bg_vae_workspace_bytes(bad, n, pg.n_slots, 1, 4, 3, 8, 8) == 0 and b"opcode" in lib.bg_last_error()
+
+
+@pytest.mark.parametrize("cls,cfg,steps", [(c[0], c[1], n) for c, n in zip(CASES, (37, 59, 29, 59))])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
+def test_program_sizes(cls, cfg, steps, dt):
+    """The step and slot counts of the four networks as BrepGen configures them: a layer added, dropped or freed late shows here."""
+    m, pg = _program(cls, cfg, dt)
+    assert (len(pg.steps), pg.n_slots) == (steps, 5)
+    if hasattr(m, "encoder"):                                  # widened as the full VAEs widen it: the same walk
+        m.n_out = 2 * m.latent
+        wide = m._program(vae._Program(), m._pack(dt)).finish()
+        assert (len(wide.steps), wide.n_slots, wide.steps[-1].n_out) == (steps, 5, 2 * m.latent)
+
+
+def test_both_executors_implement_every_primitive():
+    """A walk (`_program`) runs on the program builder and on the step-by-step driver of the GPU cross-checks: each defines all the
+    primitives itself, under the same parameter names (a walk passes most of them by keyword), and takes the block compositions from
+    the shared base."""
+    import inspect
+    from vae_stepwise import _Steps
+    for ex in (vae._Program, _Steps):
+        assert issubclass(ex, vae._Blocks)
+        assert all(callable(vars(ex).get(p)) for p in vae._Blocks.PRIMITIVES), ex
+        assert not {"resnet2d", "resconv"} & set(vars(ex)), ex
+    for p in vae._Blocks.PRIMITIVES:
+        a, b = (inspect.signature(getattr(ex, p)) for ex in (vae._Program, _Steps))
+        if p == "free":                                        # (*slots on both)
+            assert [q.kind for q in a.parameters.values()] == [q.kind for q in b.parameters.values()]
+        else:
+            assert list(a.parameters)[2:] == list(b.parameters)[2:], p     # (after self and the source slot, whatever each calls it)
+            assert [q.default for q in a.parameters.values()] == [q.default for q in b.parameters.values()], p

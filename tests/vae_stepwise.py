@@ -5,29 +5,39 @@ infrastructure only -- it cross-checks the program / the implicit-GEMM convoluti
 serves tools/vae_bench.py as the A/B baseline.
 
     from vae_stepwise import stepwise
-    y = stepwise(module, x, implicit_gemm=True)      # module: one of the four brepgen_amd VAE modules, x as module.forward takes it
+    y = stepwise(module, x, implicit_gemm=True)      # module: one of the four Fast VAE modules (or the widened encoder of a full one), x as module.forward takes it
 """
 import ctypes
-import math
 
 import torch
 
 from brepgen_amd import _lib
 import hip_ops as ops
 from brepgen_amd._lib import BG_F32, check, ptr, stream
-from brepgen_amd.vae import ACT_GELU, ACT_NONE, ACT_SILU, _CODE, _pow2
+from brepgen_amd.vae import ACT_NONE, VAE_OUT, VOP_UP1D, _Blocks, _CODE, _pow2
 
 IM2COL_BUDGET = 1 << 32        # bytes of im2col scratch per chunk of samples
 
 
-class _Steps:
-    """The primitives, written as methods over the product module `m` (weights packs, zero page, configuration)."""
+class _Steps(_Blocks):
+    """The second executor of a module's walk (`m._program`): every primitive runs its C entry point at once on torch-allocated tensors.
+    A slot is a (tensor, shape) pair, shape = (S, H, W, C) of the channels-last tensor."""
 
-    def __init__(self, m, implicit_gemm=True, im2col_budget=IM2COL_BUDGET):
-        self.m, self.implicit_gemm, self.budget = m, implicit_gemm, im2col_budget
+    def __init__(self, m, implicit_gemm=True):
+        self.m, self.implicit_gemm = m, implicit_gemm
+        self.input = self.out = None                   # the chunk a walk starts from / what its last step wrote
 
-    def __getattr__(self, name):                       # everything else (packs, decoder / encoder sub-modules, ...) is the module's
-        return getattr(self.m, name)
+    def free(self, *slots):                            # torch owns the intermediates
+        pass
+
+    def conv(self, src, conv, kh, kw, up=0, norm=None, act=ACT_NONE, res=None, stride=1, pad_mode=0, dst=None, n_out=None, pad16=64):
+        out, shape = self._conv(*src, self.packs.conv(conv, pad16), kh, kw, up, norm, act, None if res is None else res[0], stride,
+                                (0, 0) if pad_mode == 1 else None)
+        if n_out is not None:
+            out, shape = out[:, :n_out], (*shape[:3], n_out)
+        if dst == VAE_OUT:
+            self.out = out.reshape(shape)
+        return out, shape
 
     def _stats(self, x, S, P, C, norm):
         st = torch.empty(S, norm.num_groups, 2, device=x.device, dtype=torch.float32)
@@ -66,7 +76,7 @@ class _Steps:
             d.w, d.bias, d.N = ptr(pk.w), ptr(pk.b), pk.n
             d.out, d.ldc = ptr(out), pk.n
             d.add, d.ld_add = ptr(res), pk.n
-            d.dtype, d.zero_page = _CODE[pk.dtype], ptr(self._zero_page(x.device))
+            d.dtype, d.zero_page = _CODE[pk.dtype], ptr(self.m._zero_page(x.device))
             check(lib.bg_conv_gemm_fwd(ctypes.byref(d), stream()), "bg_conv_gemm_fwd")
             return out, (S, Ho, Wo, pk.n)
         a = torch.empty(rows, kh * kw * C, device=x.device, dtype=pk.dtype)
@@ -76,136 +86,43 @@ class _Steps:
         out = ops.linear(a, pk.w, pk.b, out_dtype=torch.float32, add=residual, add_div=1, n_valid=pk.n)
         return out, (S, Ho, Wo, pk.n)
 
-    def _resnet(self, x, shape, P, name, r):
-        S, H, W, C = shape
-        h, hs = self._conv(x, shape, P[name + "c1"], 3, 3, norm=r.norm1, act=ACT_SILU)
-        if name + "sc" in P:
-            x, _ = self._conv(x, shape, P[name + "sc"], 1, 1)
-        out, os_ = self._conv(h, hs, P[name + "c2"], 3, 3, norm=r.norm2, act=ACT_SILU, residual=x)
-        return out, os_
-
-    def _attn2d(self, x, shape, P, key, at):
-        """diffusers Attention of the 2-D mid block: 1 head over H*W tokens, dim_head = C."""
-        S_, H, W, C = shape
-        qkv, _ = self._conv(x, shape, P[key + "qkv"], 1, 1, norm=at.group_norm)
-        o = torch.empty(S_ * H * W, C, device=x.device, dtype=P[key + "proj"].dtype)
-        check(_lib.load().bg_small_attn(ptr(qkv), 3 * C, ptr(o), _CODE[o.dtype], S_, H * W, C, 1, 1.0 / math.sqrt(C),
-                                        stream()), "bg_small_attn")
-        return ops.linear(o, P[key + "proj"].w, P[key + "proj"].b, out_dtype=torch.float32, add=x, n_valid=C)
-
-    def _resconv(self, x, shape, P, name, r):
-        # ResConvBlock: conv k5 -> GroupNorm(1) -> GELU -> conv k5 -> GroupNorm(1) -> GELU, + (1x1) skip.
-        # group_norm_1 + GELU fold into the gather of conv_2; the trailing group_norm_2 + GELU cannot fold into the
-        # next consumer (the residual add sits in between), so it is one 1x1 "im2col" pass with the add fused.
-        h, hs = self._conv(x, shape, P[name + "c1"], 1, 5)
-        h, hs = self._conv(h, hs, P[name + "c2"], 1, 5, norm=r.group_norm_1, act=ACT_GELU)
-        S, H, W, C = hs
-        res = x
-        if name + "sk" in P:
-            res, _ = self._conv(x, shape, P[name + "sk"], 1, 1)
-        st = self._stats(h, S, H * W, C, r.group_norm_2)
+    def norm_act_add(self, src, norm, act, res):
+        h, (S, H, W, C) = src
+        st = self._stats(h, S, H * W, C, norm)
         y = torch.empty(S * H * W, C, device=h.device, dtype=torch.float32)
         check(_lib.load().bg_im2col(ptr(h), ptr(y), BG_F32, S, H, W, C, 1, 1, 0, 1, 0, 0, H, W, ptr(st),
-                                    ptr(r.group_norm_2.weight.detach().float().contiguous()),
-                                    ptr(r.group_norm_2.bias.detach().float().contiguous()), 1, ACT_GELU,
-                                    ptr(res.contiguous()), stream()),
-              "bg_im2col[norm+gelu+residual]")
-        return y, hs
+                                    ptr(norm.weight.detach().float().contiguous()), ptr(norm.bias.detach().float().contiguous()),
+                                    norm.num_groups, act, ptr(res[0].contiguous()), stream()), "bg_im2col[norm+act+residual]")
+        return y, src[1]
 
-    def _attn1d(self, x, shape, P, key, at):
+    def attn(self, src, at, heads, scale):
+        """diffusers Attention over the H*W tokens of a sample: fused q|k|v GEMM, bg_small_attn, projection GEMM + residual."""
+        x, shape = src
         S, H, W, C = shape
-        qkv, _ = self._conv(x, shape, P[key + "qkv"], 1, 1, norm=at.group_norm)
-        nh = C // 32
-        pk = P[key + "proj"]
-        o = torch.empty(S * W, C, device=x.device, dtype=pk.dtype)
-        check(_lib.load().bg_small_attn(ptr(qkv), 3 * C, ptr(o), _CODE[o.dtype], S,
-                                        H * W, C, nh, 1.0 / math.sqrt(C // nh), stream()), "bg_small_attn")
-        return ops.linear(o, pk.w, pk.b, out_dtype=torch.float32, add=x, n_valid=C)
+        qkv, proj = self.packs.attn(at)
+        t, _ = self._conv(x, shape, qkv, 1, 1, norm=at.group_norm)
+        o = torch.empty(S * H * W, C, device=x.device, dtype=proj.dtype)
+        check(_lib.load().bg_small_attn(ptr(t), 3 * C, ptr(o), _CODE[o.dtype], S, H * W, C, heads, scale, stream()), "bg_small_attn")
+        return ops.linear(o, proj.w, proj.b, out_dtype=torch.float32, add=x, n_valid=C), shape
 
-    def _chunk(self, n, per_sample_bytes):
-        return max(1, min(n, self.budget // max(1, per_sample_bytes)))
+    def resample1d(self, src, op):
+        x, (S, _, L, C) = src
+        name, Lo = ("bg_upsample1d_cubic", 2 * L) if op == VOP_UP1D else ("bg_downsample1d_cubic", L // 2)
+        y = torch.empty(S * Lo, C, device=x.device, dtype=torch.float32)
+        check(getattr(_lib.load(), name)(ptr(x), ptr(y), S, L, C, stream()), name)
+        return y, (S, 1, Lo, C)
 
-
-    def _decode_chunk_AutoencoderKLFastDecode(self, z_cl, dt):
-        """z_cl: channels-last fp32 [S,4,4,latent] -> [S,32,32,out]."""
-        P = self._pack(dt)
-        d = self.decoder
-        S = z_cl.shape[0]
-        shape = (S, z_cl.shape[1], z_cl.shape[2], self.latent)
-        x, shape = self._conv(z_cl, shape, P["pq"], 1, 1)
-        x, shape = self._conv(x, shape, P["in"], 3, 3)
-        x, shape = self._resnet(x, shape, P, "m0", d.mid_block.resnets[0])
-        x = self._attn2d(x, shape, P, "ma", d.mid_block.attentions[0])
-        x, shape = self._resnet(x, shape, P, "m1", d.mid_block.resnets[1])
-        for bi, blk in enumerate(d.up_blocks):
-            for ri, r in enumerate(blk.resnets):
-                x, shape = self._resnet(x, shape, P, f"u{bi}r{ri}", r)
-            if hasattr(blk, "upsamplers"):
-                x, shape = self._conv(x, shape, P[f"u{bi}up"], 3, 3, up=1)
-        x, shape = self._conv(x, shape, P["out"], 3, 3, norm=d.conv_norm_out, act=ACT_SILU)
-        return x.reshape(shape)
-
-    def _decode_chunk_AutoencoderKL1DFastDecode(self, z_cl, dt):
-        P = self._pack(dt)
-        d = self.decoder
-        S, L = z_cl.shape[0], z_cl.shape[1]
-        shape = (S, 1, L, self.latent)
-        x, shape = self._conv(z_cl, shape, P["pq"], 1, 1)
-        x, shape = self._conv(x, shape, P["in"], 1, 3)
-        for i in range(6):
-            x, shape = self._resconv(x, shape, P, f"m{i}", d.mid_block.resnets[i])
-            x = self._attn1d(x, shape, P, f"a{i}", d.mid_block.attentions[i])
-        for bi, blk in enumerate(d.up_blocks):
-            for ri, r in enumerate(blk.resnets):
-                x, shape = self._resconv(x, shape, P, f"u{bi}r{ri}", r)
-            S_, _, L_, C = shape
-            y = torch.empty(S_ * 2 * L_, C, device=x.device, dtype=torch.float32)
-            check(_lib.load().bg_upsample1d_cubic(ptr(x), ptr(y), S_, L_, C, stream()), "bg_upsample1d_cubic")
-            x, shape = y, (S_, 1, 2 * L_, C)
-        x, shape = self._conv(x, shape, P["out"], 1, 3, norm=d.conv_norm_out, act=ACT_SILU)
-        return x.reshape(shape[0], shape[2], shape[3])
-
-    def _encode_chunk_AutoencoderKLFastEncode(self, x_cl, dt):
-        P, e = self._pack(dt), self.encoder
-        S = x_cl.shape[0]
-        shape = (S, x_cl.shape[1], x_cl.shape[2], self.in_ch)
-        x, shape = self._conv(x_cl, shape, P["in"], 3, 3)
-        for bi, blk in enumerate(e.down_blocks):
-            for ri, r in enumerate(blk.resnets):
-                x, shape = self._resnet(x, shape, P, f"d{bi}r{ri}", r)
-            if hasattr(blk, "downsamplers"):                      # Downsample2D: pad (0,1,0,1), conv 3x3 stride 2
-                x, shape = self._conv(x, shape, P[f"d{bi}dn"], 3, 3, stride=2, pad=(0, 0))
-        x, shape = self._resnet(x, shape, P, "m0", e.mid_block.resnets[0])
-        x = self._attn2d(x, shape, P, "ma", e.mid_block.attentions[0])
-        x, shape = self._resnet(x, shape, P, "m1", e.mid_block.resnets[1])
-        x, shape = self._conv(x, shape, P["out"], 3, 3, norm=e.conv_norm_out, act=ACT_SILU)
-        x, shape = self._conv(x, shape, P["q"], 1, 1)
-        return x.reshape(shape)[..., : self.latent]               # DiagonalGaussianDistribution(moments).mode() = mean
-
-    def _encode_chunk_AutoencoderKL1DFastEncode(self, x_cl, dt):
-        P, e = self._pack(dt), self.encoder
-        S, L = x_cl.shape[0], x_cl.shape[1]
-        shape = (S, 1, L, self.in_ch)
-        x, shape = self._conv(x_cl, shape, P["in"], 1, 3)
-        for bi, blk in enumerate(e.down_blocks):
-            S_, _, L_, C = shape
-            y = torch.empty(S_ * (L_ // 2), C, device=x.device, dtype=torch.float32)
-            check(_lib.load().bg_downsample1d_cubic(ptr(x), ptr(y), S_, L_, C, stream()), "bg_downsample1d_cubic")
-            x, shape = y, (S_, 1, L_ // 2, C)
-            for ri, r in enumerate(blk.resnets):
-                x, shape = self._resconv(x, shape, P, f"d{bi}r{ri}", r)
-        for i in range(6):
-            x, shape = self._resconv(x, shape, P, f"m{i}", e.mid_block.resnets[i])
-            x = self._attn1d(x, shape, P, f"a{i}", e.mid_block.attentions[i])
-        x, shape = self._conv(x, shape, P["out"], 1, 3, norm=e.conv_norm_out, act=ACT_SILU)
-        x, shape = self._conv(x, shape, P["q"], 1, 1)
-        return x.reshape(shape[0], shape[2], shape[3])[..., : self.latent]
-
+    def run(self, x_cl, dt):
+        """One chunk x_cl [S, (H,) W, C] through the module's walk -> its output, channels-last [S, (H,) W, C']."""
+        self.input = (x_cl, (x_cl.shape[0], 1, *x_cl.shape[1:]) if x_cl.dim() == 3 else tuple(x_cl.shape))
+        self.m._program(self, self.m._pack(dt))
+        return self.out if x_cl.dim() == 4 else self.out.squeeze(1)
 
 
 def stepwise(m, x, implicit_gemm=True, im2col_budget=IM2COL_BUDGET):
-    """module.forward(x) through the step-by-step driver (chunked against `im2col_budget` like the round-1 path)."""
-    st = _Steps(m, implicit_gemm, im2col_budget)
+    """module.forward(x) through the step-by-step driver (chunked against `im2col_budget` like the round-1 path).  The layout and the chunk
+    estimate go by the module's class name: the widened encoder of a full VAE (`full._runners[0]`) is an instance of the Fast encoder class."""
+    st = _Steps(m, implicit_gemm)
     dt = m._dtype()
     cls = type(m).__name__
     es = 4 if dt == torch.float32 else 2
@@ -213,17 +130,12 @@ def stepwise(m, x, implicit_gemm=True, im2col_budget=IM2COL_BUDGET):
     two_d = cls in ("AutoencoderKLFastDecode", "AutoencoderKLFastEncode")
     x_cl = (x.permute(0, 2, 3, 1) if two_d else x.permute(0, 2, 1)).contiguous()
     n = x_cl.shape[0]
-    if cls == "AutoencoderKLFastDecode":
-        side = x_cl.shape[1] * 2 ** (len(m.block_out) - 1)
-        worst, fn = side * side * 9 * max(m.block_out[0] * 2, m.block_out[0]) * es, st._decode_chunk_AutoencoderKLFastDecode
-    elif cls == "AutoencoderKL1DFastDecode":
-        length = x_cl.shape[1] * 2 ** len(m.block_out)
-        worst, fn = length * 5 * m.block_out[-1] * es, st._decode_chunk_AutoencoderKL1DFastDecode
-    elif cls == "AutoencoderKLFastEncode":
-        worst, fn = x_cl.shape[1] * x_cl.shape[1] * 9 * m.block_out[0] * es, st._encode_chunk_AutoencoderKLFastEncode
-    else:
-        worst, fn = x_cl.shape[1] * 5 * m.block_out[-1] * es, st._encode_chunk_AutoencoderKL1DFastEncode
-    step = st._chunk(n, worst)
-    outs = [fn(x_cl[i:i + step].contiguous(), dt) for i in range(0, n, step)]
+    side = x_cl.shape[1]
+    worst = {"AutoencoderKLFastDecode": (side * 2 ** (len(m.block_out) - 1)) ** 2 * 9 * m.block_out[0] * 2 * es,
+             "AutoencoderKL1DFastDecode": side * 2 ** len(m.block_out) * 5 * m.block_out[-1] * es,
+             "AutoencoderKLFastEncode": side * side * 9 * m.block_out[0] * es,
+             "AutoencoderKL1DFastEncode": side * 5 * m.block_out[-1] * es}[cls]     # bytes of one sample's largest im2col matrix
+    step = max(1, min(n, im2col_budget // max(1, worst)))
+    outs = [st.run(x_cl[i:i + step].contiguous(), dt) for i in range(0, n, step)]
     y = torch.cat(outs) if len(outs) > 1 else outs[0]
     return (y.permute(0, 3, 1, 2) if two_d else y.permute(0, 2, 1)).contiguous()
