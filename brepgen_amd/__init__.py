@@ -11,6 +11,7 @@ Drop-in for the reference's call surface on that path only:
     CADStore / augment_points (dataset.py: load_data, the six datasets) (dataset.py) -> bg_cad_filter / bg_batch_plan / bg_batch_gather
     dedup_cads / unique_items (data_process/deduplicate_*.py)       (deduplicate.py) -> bg_points_sha256 / bg_digest_group_keys / bg_first_occurrence
     optim.AdamW / optim.GradScaler / optim.clip_grad_norm_ (trainer.py's update) (optim.py) -> bg_mt_grad_stats / bg_mt_adamw_step / bg_optim_finish
+    nn.MultiheadAttention in net.train() (attention core, dropout, backward) (attention.py) -> bg_attn_train_fwd / bg_attn_bwd
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from . import optim  # noqa: F401
@@ -40,6 +41,9 @@ __all__ += list(_DATASET)
 # data_process/deduplicate_cad.py and deduplicate_surfedge.py (deduplicate.py; `python -m brepgen_amd.deduplicate`)
 _DEDUPLICATE = ("point_digests", "cad_keys", "first_occurrence", "dedup_cads", "unique_items")
 __all__ += list(_DEDUPLICATE)
+# the attention core for training: forward with dropout + backward on the device (attention.py)
+_ATTENTION = ("self_attention", "MultiheadSelfAttention", "use_device_attention")
+__all__ += list(_ATTENTION)
 
 
 def __getattr__(name):
@@ -58,4 +62,7 @@ def __getattr__(name):
     if name in _DEDUPLICATE:
         from . import deduplicate
         return getattr(deduplicate, name)
+    if name in _ATTENTION:
+        from . import attention
+        return getattr(attention, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -13,6 +13,7 @@ BG_F32, BG_F16, BG_BF16 = 0, 1, 2
 BG_ACT_NONE, BG_ACT_RELU = 0, 1
 BG_SURFPOS, BG_SURFZ, BG_EDGEPOS, BG_EDGEZ = 0, 1, 2, 3
 BG_MAX_LAYERS, BG_MAX_EMBEDS = 12, 5
+BG_ATTN_BWD_AUTO, BG_ATTN_BWD_GENERAL, BG_ATTN_BWD_SHORT = 0, 1, 2      # enum bg_attn_bwd_variant
 
 vp, fp, i64p, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # device pointers travel as integers
 
@@ -183,6 +184,12 @@ _SIGNATURES = {
     "bg_mt_adamw_step": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_double, C.c_double, C.c_double, vp]),
     "bg_optim_finish": (C.c_int, [vp, C.c_int, vp, vp, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp]),
     "bg_mt_scale_grads": (C.c_int, [vp, vp, C.c_int, vp, C.c_float, fp, vp]),
+    "bg_attn_train_fwd": (C.c_int, [vp, u8p, vp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_ulonglong, C.c_uint,
+                                    C.c_longlong, vp]),
+    "bg_attn_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "bg_attn_bwd": (C.c_int, [vp, u8p, fp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_ulonglong, C.c_uint,
+                              C.c_longlong, C.c_int, vp, C.c_size_t, vp]),
+    "bg_attn_dropout_mask": (C.c_int, [u8p, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_uint, C.c_longlong, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

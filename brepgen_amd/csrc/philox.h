@@ -1,6 +1,8 @@
 // Philox4x32-10 and the 32-bit word -> uniform map, defined once for the kernels that draw on the device (rng.hip: bg_philox_randn,
 // mesh_sample.hip: bg_mesh_sample, vae_loss.hip: bg_vae_posterior).  Every user keys the generator with the run's seed and builds its counter from GLOBAL indices plus a
 // 16-bit domain tag in the top half-word of word 3, so no two users ever share a counter.  oracle/philox.py restates it in numpy.
+// Tags in use: 0xB9E5 bg_philox_randn / bg_vae_posterior, 0x5A3D bg_mesh_sample, 0xDA7A bg_batch_plan, 0xDA7B bg_points_rotate_normalize,
+// 0xAD70 the attention dropout mask (attn_train.hip: bg_attn_train_fwd / bg_attn_bwd / bg_attn_dropout_mask).
 #pragma once
 #include "bg_common.h"
 

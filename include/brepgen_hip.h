@@ -142,6 +142,50 @@ int bg_attn_fwd(const void* qkv, const uint8_t* key_pad, void* out, int B, int N
  * with offsets[b] == offsets[b+1] costs nothing. */
 int bg_attn_varlen_fwd(const void* qkv, const uint8_t* key_pad, void* out, int B, int N, int dtype,
                        const int* offsets, bg_stream_t stream);
+
+/* ---- the attention core for TRAINING (csrc/attn_train.hip): forward that keeps the row log-sum-exp, dropout on the probabilities
+ * (nn.MultiheadAttention(dropout=0.1) in net.train(), network.py:1076-1078), and the backward.  Layout as bg_attn_fwd: qkv
+ * [B*N, 2304], key_pad uint8 [B, N] (1 = padded key) or NULL, out [B*N, 768]; dtype BG_BF16 / BG_F16 (MFMA, fp32 accumulation) or
+ * BG_F32 (VALU restatement, sums accumulated in fp64).  The score is S = scale * q.k^T: q is NOT pre-scaled here.  N >= 1; B == 0 returns 0 without a
+ * launch.  Nothing is allocated, no atomics: every output element has one writer and a fixed summation order, so two calls give the
+ * same bits and a sample's results depend on that sample's rows alone.
+ *
+ * The dropout mask M is a pure function of (seed, draw_id, GLOBAL sample index g = first_sample + b, head, query, key): one
+ * Philox4x32-10 block, key = seed, counter = (query << 16 | kb, low 32 bits of g, draw_id, 0xAD700000 | head << 12 | bits 32..43 of g),
+ * gives the four words of keys 4 kb .. 4 kb + 3; a key is KEPT iff its word >= floor(dropout_p * 2^32) (formed in double), and kept
+ * probabilities are multiplied by float(1 / (1 - dropout_p)).  0 <= dropout_p < 1; dropout_p == 0 runs kernels compiled without the
+ * generator.  With dropout_p > 0, N <= 65536. */
+
+/* Forward.  Reads qkv rows 0 .. B*N-1 and key_pad.  Writes out [B*N, 768] = (softmax(S) o M / (1 - p)) V and lse fp32 [B, 12, N] =
+ * row maximum + log of the row sum of exp, taken BEFORE dropout (the softmax normaliser does not see the mask, as in torch).  A
+ * sample whose keys are all padded gives out = 0 and lse = 0. */
+int bg_attn_train_fwd(const void* qkv, const uint8_t* key_pad, void* out, float* lse, int B, int N, int dtype, float scale,
+                      double dropout_p, unsigned long long seed, unsigned draw_id, long long first_sample, bg_stream_t stream);
+/* Scratch of bg_attn_bwd, rounded up to 256 bytes: delta [B, 12, N] fp32; BG_F32: followed by the row maximum and the row sum of
+ * exp, [B, 12, N] each (the fp32 kernels normalise as torch does, P = exp(S - max) / sum, and do not read lse: rounded to fp32 it would
+ * cost several ulp in every P of a row).  0 for arguments bg_attn_bwd rejects. */
+size_t bg_attn_bwd_workspace_bytes(int B, int N, int dtype);
+/* Backward.  Reads qkv and key_pad, lse as bg_attn_train_fwd left it, dout [B*N, 768] (dtype of qkv) and the same dropout key; the
+ * forward's out is not needed.  Writes dqkv [B*N, 2304] (dq | dk | dv, dtype of qkv), EVERY element, rows of padded tokens included
+ * (nobody has to zero it first), and the workspace as bg_attn_bwd_workspace_bytes lays it out.  P = exp(S - lse) recomputed in fp32;
+ * dV = (P o M/(1-p))^T dO;  dP = (dO V^T) o M/(1-p);  delta_i = sum_j P_ij dP_ij (= sum_d dO_id O_id, summed as torch's softmax
+ * backward sums it);  dS = P o (dP - delta);  dQ = scale dS K;  dK = scale dS^T Q.  Padded keys have P = 0 exactly: their dK and
+ * dV rows are exactly 0, and an all-padded sample's gradients are all 0.  A non-finite dout makes delta, dP and dS of its sample
+ * non-finite: that sample's gradients contain inf / NaN (a GradScaler's found_inf trips), the other samples' stay finite.
+ * General path, any N, two launches: dQ (a workgroup owns 128 queries of one (sample, head) and walks the keys twice: delta, then dS
+ * and dQ); dK / dV (a workgroup owns 128 keys and walks the queries).  Short path, N <= 64 and 16-bit operands, ONE launch with
+ * nothing recomputed: a workgroup holds one (sample, head), P~ and dS cross the LDS once; its dQ is the general path's bit for bit,
+ * its dK / dV sum the queries in another order.  variant picks: BG_ATTN_BWD_AUTO (the short path where it applies),
+ * BG_ATTN_BWD_GENERAL, BG_ATTN_BWD_SHORT (BG_E_SHAPE where it does not apply).  first_sample + B <= 2^44. */
+enum bg_attn_bwd_variant { BG_ATTN_BWD_AUTO = 0, BG_ATTN_BWD_GENERAL = 1, BG_ATTN_BWD_SHORT = 2 };
+int bg_attn_bwd(const void* qkv, const uint8_t* key_pad, const float* lse, const void* dout, void* dqkv, int B, int N,
+                int dtype, float scale, double dropout_p, unsigned long long seed, unsigned draw_id, long long first_sample,
+                int variant, void* workspace, size_t workspace_bytes, bg_stream_t stream);
+/* The keep mask itself, uint8 [B, 12, N, N] (1 = kept), from the same key: the replay / test entry (a host can reproduce a run's
+ * masks from it, or from the counter layout above).  Writes every element; reads nothing.  N <= 65536. */
+int bg_attn_dropout_mask(uint8_t* mask, int B, int N, double dropout_p, unsigned long long seed, unsigned draw_id, long long first_sample,
+                         bg_stream_t stream);
+
 /* QKV projection with the LayerNorm fold + self-attention in ONE launch (csrc/qkv_attn.hip): sequences of an even length
  * N <= 64, all B of them equally long; key_pad (may be NULL) as bg_attn_fwd's.  x_hi [B*N, 768] raw 16-bit rows, w_qkv [2304, 768] /
  * bias / colsum as bg_gemm_ex_fwd's fold operands, stats_in [12][B*N][2] the row statistics partials of x; out [B*N, 768] = what
