@@ -12,17 +12,18 @@
 //     permutation as long as both operands agree, so the A operand (V^T rows from LDS) is simply read in the key
 //     order the lane's score registers already have (two 8-byte reads) -- no cross-lane shuffle of P at all;
 //   * K tile in LDS: 64 keys x 128 B, LDS-DMA + 16-byte XOR swizzle (the GEMMs' scheme and helpers: gemm16.h);
-//     V tile in LDS: transposed [64 d][64 keys], row stride 68 bf16 so the 32 d-rows a half-wave reads with
-//     ds_read_b64 fall on 32 distinct bank pairs.
+//     V tile in LDS: transposed [64 d][64 keys], row stride TR_LD.
+// The register-to-key convention (which key a lane's score register r holds), the strides and the row-fragment load are attn_tile.h's,
+// shared with the training kernels of attn_train.hip.  attn16_kernel keeps its OWN text of the other tile steps (K-fragment read,
+// transposing write, online-softmax sub-tile, P V accumulate, store): it is on the product path, and behind a helper each of them
+// came out of hipcc as another instruction stream.  at_fwd16_kernel states the same arithmetic: with scale 1
+// and no dropout it gives this kernel's bits (asserted).  attn16_long_kernel is hand-scheduled and keeps its own text too.
 // fp32 kernel: exact VALU restatement for the fp32 parity mode (not a performance path).
-#include "gemm16.h"
-#include <math.h>
+#include "attn_tile.h"
 
 namespace bg {
 
-constexpr int QKV_LD = 3 * BG_D_MODEL;     // 2304
-constexpr int VS = 68;                     // V^T row stride (bf16 elements)
-constexpr int HEAD_LDS = 64 * 128 + 64 * VS * 2;   // K tile + V^T tile bytes per head slot = 16896
+constexpr int HEAD_LDS = AT_RM + AT_TR;    // K tile + V^T tile bytes per head slot = 16896
 
 template <int WPH, bool F16>
 __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const void* __restrict__ qkv_, const uint8_t* __restrict__ key_pad,
@@ -57,14 +58,12 @@ __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const voi
     }
     const T* base = qkv + row_base * QKV_LD + head * 64;
 
-    // Q fragments (B operand of S^T = K Q^T): lane = (query l&31, k-chunk h) for each 16-wide slice of d
+    // Q fragments (B operand of S^T = K Q^T)
     V8 qf[4];
     {
         int qrow = q0 + (lane & 31);
         qrow = qrow < N ? qrow : N - 1;
-        const T* qp = base + (size_t)qrow * QKV_LD;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + (ks * 2 + h) * 8);
+        at_row_frags<F16>(base + (size_t)qrow * QKV_LD, h, qf);
     }
     // K fragment read offsets (A operand): key row l&31 (+32 for the second sub-tile)
     int k_off[2], k_sw[2];
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const voi
             key = key < N ? key : N - 1;
             const V8 v = *reinterpret_cast<const V8*>(base + (size_t)key * QKV_LD + 2 * BG_D_MODEL + dc * 8);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) vt[(dc * 8 + e) * VS + row] = v[e];
+            for (int e = 0; e < 8; ++e) vt[(dc * 8 + e) * TR_LD + row] = v[e];
         }
         if (tid < 64) {
             const int key = kt * 64 + tid;
@@ -126,7 +125,7 @@ __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const voi
                 const V8 kf = *reinterpret_cast<const V8*>(ktile + k_off[sub] + (((ks * 2 + h) ^ k_sw[sub]) << 4));
                 s = E::mfma(kf, qf[ks], s);
             }
-            // register r <-> key sub*32 + (r&3) + 8*(r>>2) + 4*h of query (lane & 31)
+            // which key register r holds: attn_tile.h's tile convention; 8 g4 + 4 h here and in the store = at_walked(4 g4, h)
             float mloc = -INFINITY;
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(256, WPH == 1 ? 2 : 4) void attn16_kernel(const voi
                 for (int e = 0; e < 8; ++e) pb[e] = (T)s[8 * sl + e];
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    const T* vrow = vt + (dt * 32 + (lane & 31)) * VS + sub * 32 + 16 * sl + 4 * h;
+                    const T* vrow = vt + (dt * 32 + (lane & 31)) * TR_LD + sub * 32 + 16 * sl + 4 * h;
                     const V4 lo = *reinterpret_cast<const V4*>(vrow);
                     const V4 hi = *reinterpret_cast<const V4*>(vrow + 8);
                     V8 va;
@@ -529,9 +528,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
         lsum += e;
     }
     const float l = wave_sum(lsum);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    at_wave_lds_sync();
     float acc = 0.f;                                   // lane = d
     for (int j = 0; j < N; ++j) acc = fmaf(p[j], base[(size_t)j * QKV_LD + 2 * BG_D_MODEL + lane], acc);
     out[(row_base + q) * BG_D_MODEL + head * 64 + lane] = l > 0.f ? acc / l : 0.f;
@@ -565,10 +562,9 @@ int attention(const void* qkv, const uint8_t* key_pad, void* out, int B, int N, 
             const dim3 grid((unsigned)(nqb * 8 * ((B * BG_N_HEAD + 7) / 8)));
             const bool masked = key_pad != nullptr && offsets == nullptr;
             const int eighths = g_tune[TUNE_ATTN_WALK] == 1;
-            if (f16 && masked) hipLaunchKernelGGL((attn16_long_kernel<true, true>), grid, dim3(256), 0, s, qkv, key_pad, out, B, N, nqb, offsets, eighths);
-            else if (f16) hipLaunchKernelGGL((attn16_long_kernel<true, false>), grid, dim3(256), 0, s, qkv, key_pad, out, B, N, nqb, offsets, eighths);
-            else if (masked) hipLaunchKernelGGL((attn16_long_kernel<false, true>), grid, dim3(256), 0, s, qkv, key_pad, out, B, N, nqb, offsets, eighths);
-            else hipLaunchKernelGGL((attn16_long_kernel<false, false>), grid, dim3(256), 0, s, qkv, key_pad, out, B, N, nqb, offsets, eighths);
+            with_bools(f16, masked, [&](auto F16, auto MASKED) {
+                hipLaunchKernelGGL((attn16_long_kernel<F16(), MASKED()>), grid, dim3(256), 0, s, qkv, key_pad, out, B, N, nqb, offsets, eighths);
+            });
         }
         return launch_status("attn16");
     }

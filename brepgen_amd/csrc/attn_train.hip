@@ -8,7 +8,9 @@
 //             backward sums it: exact cancellation in dS when a row has one key, and independent of the rounding of O),
 //             dV = (P o M / (1-p))^T dO,  dP = (dO V^T) o M / (1-p),  dS = P o (dP - delta),  dQ = scale dS K,  dK = scale dS^T Q
 //
-// 16-bit kernels (bf16 / fp16 operands into v_mfma_f32_32x32x16, fp32 accumulation), all with attn.hip's two ideas:
+// 16-bit kernels (bf16 / fp16 operands into v_mfma_f32_32x32x16, fp32 accumulation), all on the tile convention, the staging and the
+// fragment reads of attn_tile.h; the short backward also on its element step, hi + lo split and store, of which the forward and the
+// general backward keep their own text where a helper changed their instruction stream (listed in attn_tile.h):
 //   * scores are computed with the WALKED index on the accumulator registers and the OWNED index on the lane
 //     (forward and dQ: a wave owns 32 queries and walks the keys, S^T = K Q^T; dK/dV: a wave owns 32 keys and walks the queries,
 //     S = Q K^T), so whatever belongs to the owned row -- running max and sum, lse, delta, the key's padding flag -- is lane-local;
@@ -23,16 +25,11 @@
 //   Backward, N <= 64 (the face trainers): one launch, one workgroup per (sample, head), nothing recomputed (at_bwd16_short_kernel);
 //   measured faster than the general path at N = 30, 50 and 64 (profiles/r13/attn_bwd_bench.json), so BG_ATTN_BWD_AUTO takes it.
 // fp32 kernels: VALU restatement (one wave per owned row, fp64 accumulation), the parity mode of the 16-bit path -- not a performance path.
-#include "gemm16.h"
+#include "attn_tile.h"
 #include "philox.h"
-#include <math.h>
 
 namespace bg {
 
-constexpr int AT_QKV_LD = 3 * BG_D_MODEL;      // 2304
-constexpr int AT_VS = 68;                      // row stride of a transposed tile image (16-bit elements): attn.hip's V^T image
-constexpr int AT_RM = 64 * 128;                // row-major tile image: 64 rows x 128 B, 16-byte chunks XOR-swizzled (gemm16.h)
-constexpr int AT_TR = 64 * AT_VS * 2;          // transposed tile image [64 d][AT_VS]
 constexpr uint32_t AT_TAG = 0xAD700000u;       // Philox domain tag of the dropout mask (philox.h lists the tags in use)
 constexpr int AT_SHORT_AUTO_N = 64;            // BG_ATTN_BWD_AUTO: 16-bit sequences up to this length take the one-launch kernel
 constexpr int AT_MAX_N_DROP = 65536;           // the counter holds the query in 16 bits and the 4-key block in 16 bits
@@ -71,43 +68,8 @@ __global__ __launch_bounds__(256) void at_mask_kernel(uint8_t* __restrict__ mask
         if (4 * kb + e < N) p[e] = (uint8_t)((nib >> e) & 1u);
 }
 
-// ---- tile staging of the 16-bit kernels: 64 rows (tile row r = row min(r0 + r, N - 1) of the sample) x 64 elements of `src` ----
-// RM: row-major image, chunk c of row r at chunk c ^ swz_term(r);  TR: transposed image tr[d][r]
-template <typename T, typename V8, bool RM, bool TR>
-__device__ __forceinline__ void at_stage(const T* __restrict__ src, int ld, int r0, int N, unsigned char* img, T* tr, int tid) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int idx = j * 256 + tid;
-        const int row = idx >> 3, c = idx & 7;
-        int g = r0 + row;
-        g = g < N ? g : N - 1;
-        const V8 v = *reinterpret_cast<const V8*>(src + (size_t)g * ld + c * 8);
-        if (RM) *reinterpret_cast<V8*>(img + row * 128 + ((c ^ swz_term(row)) << 4)) = v;
-        if (TR) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) tr[(c * 8 + e) * AT_VS + row] = v[e];
-        }
-    }
-}
-// A fragment of a row-major image: tile row `row`, 16-byte chunk `chunk`
-template <typename V8> __device__ __forceinline__ V8 at_frag_rm(const unsigned char* img, int row, int chunk) {
-    return *reinterpret_cast<const V8*>(img + row * 128 + ((chunk ^ swz_term(row)) << 4));
-}
-// A fragment of a transposed image: column d, tile rows w0 .. w0 + 3 and w0 + 8 .. w0 + 11 -- the order in which a lane's accumulator
-// registers 8 sl .. 8 sl + 7 hold the walked index (w0 = 32 sub + 16 sl + 4 h)
-template <typename T, typename V8, typename V4> __device__ __forceinline__ V8 at_frag_tr(const T* tr, int d, int w0) {
-    const T* p = tr + d * AT_VS + w0;
-    const V4 lo = *reinterpret_cast<const V4*>(p);
-    const V4 hi = *reinterpret_cast<const V4*>(p + 8);
-    V8 a;
-    a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
-    a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
-    return a;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Training forward, 16-bit.  grid (ceil(N / 128), 12, B); a wave owns 32 queries of (b, head) and walks the key tiles of 64.
-// accumulator register r of a 32-key sub-tile <-> key 32 sub + (r & 3) + 8 (r >> 2) + 4 h of query (lane & 31), h = lane >> 5
 // ------------------------------------------------------------------------------------------------
 template <bool F16, bool DROP>
 __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict__ qkv_, const uint8_t* __restrict__ key_pad,
@@ -115,7 +77,6 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
     using E = Elem<F16>;
     using T = typename E::T;
     using V8 = typename E::V8;
-    using V4 = typename E::V4;
     __shared__ __attribute__((aligned(16))) unsigned char lds[AT_RM + AT_TR + 256];
     unsigned char* kimg = lds;
     T* vtr = reinterpret_cast<T*>(lds + AT_RM);
@@ -128,16 +89,12 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
     const int b = blockIdx.z, head = blockIdx.y;
     const int q0 = blockIdx.x * 128 + wave * 32;
     const size_t row_base = (size_t)b * N;
-    const T* base = qkv + row_base * AT_QKV_LD + head * 64;
+    const T* base = qkv + row_base * QKV_LD + head * 64;
     const int q = q0 + l31;
     const unsigned long long g = dk.first + (unsigned long long)b;
 
     V8 qf[4];
-    {
-        const T* qp = base + (size_t)(q < N ? q : N - 1) * AT_QKV_LD;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + (ks * 2 + h) * 8);
-    }
+    at_row_frags<F16>(base + (size_t)(q < N ? q : N - 1) * QKV_LD, h, qf);
     f32x16 o[2];
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -148,8 +105,8 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
     const int nkt = (N + 63) / 64;
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();                                   // previous tile fully consumed
-        at_stage<T, V8, true, false>(base + BG_D_MODEL, AT_QKV_LD, kt * 64, N, kimg, nullptr, tid);
-        at_stage<T, V8, false, true>(base + 2 * BG_D_MODEL, AT_QKV_LD, kt * 64, N, nullptr, vtr, tid);
+        at_stage<F16, 256, true, false>(base + BG_D_MODEL, QKV_LD, kt * 64, N, kimg, nullptr, tid);
+        at_stage<F16, 256, false, true>(base + 2 * BG_D_MODEL, QKV_LD, kt * 64, N, nullptr, vtr, tid);
         if (tid < 64) {
             const int key = kt * 64 + tid;
             const bool dead = key >= N || (key_pad != nullptr && key_pad[row_base + key] != 0);
@@ -164,7 +121,8 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) s = E::mfma(at_frag_rm<V8>(kimg, sub * 32 + l31, ks * 2 + h), qf[ks], s);
+            for (int ks = 0; ks < 4; ++ks) s = E::mfma(at_frag_rm<F16>(kimg, sub * 32 + l31, ks * 2 + h), qf[ks], s);
+            // online-softmax sub-tile, P V accumulate and the store are this kernel's own text (as in attn16_kernel: attn_tile.h)
             float mloc = -INFINITY;
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -188,7 +146,7 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
             if (DROP) {
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
-                    const unsigned nib = keep_nibble(dk, g, head, q, (kt * 64 + sub * 32 + 8 * g4 + 4 * h) >> 2);
+                    const unsigned nib = keep_nibble(dk, g, head, q, (kt * 64 + sub * 32 + at_walked(4 * g4, h)) >> 2);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) s[4 * g4 + e] = ((nib >> e) & 1u) ? s[4 * g4 + e] : 0.f;
                 }
@@ -204,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
                 for (int e = 0; e < 8; ++e) pb[e] = (T)s[8 * sl + e];
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt)
-                    o[dt] = E::mfma(at_frag_tr<T, V8, V4>(vtr, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h), pb, o[dt]);
+                    o[dt] = E::mfma(at_frag_tr<F16>(vtr, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h), pb, o[dt]);
             }
         }
     }
@@ -218,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4)
-                *reinterpret_cast<V4*>(op + dt * 32 + 8 * g4 + 4 * h) =
+                *reinterpret_cast<typename E::V4*>(op + dt * 32 + 8 * g4 + 4 * h) =
                     E::pack4(o[dt][4 * g4 + 0] * inv, o[dt][4 * g4 + 1] * inv, o[dt][4 * g4 + 2] * inv, o[dt][4 * g4 + 3] * inv);
     }
 }
@@ -230,7 +188,6 @@ __global__ __launch_bounds__(256, 2) void at_fwd16_kernel(const void* __restrict
 //                        (written to the workspace for the dK/dV kernel), the second one forms dS and dQ
 //   DKV = true  (dK/dV): owned = keys    (X = K, Y = V in registers), walked = queries (A1 = Q, A2 = dO tiles in LDS)
 //                        S = A1 X^T, dP = A2 Y^T, dV^T += A2^T P~, dK^T += A1^T dS
-// register r of a 32-row sub-tile <-> walked index 32 sub + (r & 3) + 8 (r >> 2) + 4 h
 // ------------------------------------------------------------------------------------------------
 template <bool F16, bool DROP, bool DKV>
 __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict__ qkv_, const uint8_t* __restrict__ key_pad,
@@ -240,7 +197,6 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
     using E = Elem<F16>;
     using T = typename E::T;
     using V8 = typename E::V8;
-    using V4 = typename E::V4;
     constexpr int LDS_BYTES = 2 * AT_RM + (DKV ? 2 : 1) * AT_TR + 512;
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
     unsigned char* img1 = lds;
@@ -259,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
     const int own0 = blockIdx.x * 128 + wave * 32;
     const int own = own0 + l31, ownc = own < N ? own : N - 1;
     const size_t row_base = (size_t)b * N;
-    const T* qb = qkv + row_base * AT_QKV_LD + head * 64;            // Q; K at + 768, V at + 1536
+    const T* qb = qkv + row_base * QKV_LD + head * 64;               // Q; K at + 768, V at + 1536
     const T* dob = dout + row_base * BG_D_MODEL + head * 64;
     const float* lse_b = lse + ((size_t)b * BG_N_HEAD + head) * N;
     float* del_b = delta + ((size_t)b * BG_N_HEAD + head) * N;       // written by the dQ kernel, read by the dK/dV kernel
@@ -267,11 +223,13 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
 
     const T* a1 = DKV ? qb : qb + BG_D_MODEL;
     const T* a2 = DKV ? dob : qb + 2 * BG_D_MODEL;
-    const int ld2 = DKV ? BG_D_MODEL : AT_QKV_LD;
+    const int ld2 = DKV ? BG_D_MODEL : QKV_LD;
+    // the x / y row fragments (loads interleaved), the element step, the hi + lo split and the store are this kernel's own text: behind
+    // attn_tile.h's helpers its instruction stream changed and the dropout instantiations measured slower
     V8 xf[4], yf[4];
     {
-        const T* xp = (DKV ? qb + BG_D_MODEL : qb) + (size_t)ownc * AT_QKV_LD;
-        const T* yp = DKV ? qb + 2 * BG_D_MODEL + (size_t)ownc * AT_QKV_LD : dob + (size_t)ownc * BG_D_MODEL;
+        const T* xp = (DKV ? qb + BG_D_MODEL : qb) + (size_t)ownc * QKV_LD;
+        const T* yp = DKV ? qb + 2 * BG_D_MODEL + (size_t)ownc * QKV_LD : dob + (size_t)ownc * BG_D_MODEL;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             xf[ks] = *reinterpret_cast<const V8*>(xp + (ks * 2 + h) * 8);
@@ -296,9 +254,9 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
         const bool sum_delta = !DKV && pass == 0;
         for (int t = 0; t < nwt; ++t) {
             __syncthreads();                                   // previous tile fully consumed
-            if (sum_delta) at_stage<T, V8, true, false>(a1, AT_QKV_LD, t * 64, N, img1, tr1, tid);
-            else at_stage<T, V8, true, true>(a1, AT_QKV_LD, t * 64, N, img1, tr1, tid);
-            at_stage<T, V8, true, DKV>(a2, ld2, t * 64, N, img2, tr2, tid);
+            if (sum_delta) at_stage<F16, 256, true, false>(a1, QKV_LD, t * 64, N, img1, tr1, tid);
+            else at_stage<F16, 256, true, true>(a1, QKV_LD, t * 64, N, img1, tr1, tid);
+            at_stage<F16, 256, true, DKV>(a2, ld2, t * 64, N, img2, tr2, tid);
             if (tid < 64) {
                 const int w = t * 64 + tid;
                 if (DKV) {
@@ -320,35 +278,35 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
                 for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
-                    s = E::mfma(at_frag_rm<V8>(img1, sub * 32 + l31, ks * 2 + h), xf[ks], s);
-                    dp = E::mfma(at_frag_rm<V8>(img2, sub * 32 + l31, ks * 2 + h), yf[ks], dp);
+                    s = E::mfma(at_frag_rm<F16>(img1, sub * 32 + l31, ks * 2 + h), xf[ks], s);
+                    dp = E::mfma(at_frag_rm<F16>(img2, sub * 32 + l31, ks * 2 + h), yf[ks], dp);
                 }
                 unsigned keep[4] = {0xFFFFu, 0xFFFFu, 0xFFFFu, 0xFFFFu};   // DKV: keep[e] bit 4 g4 + (lane & 3); dQ: keep[g4] bit e
                 if (DROP) {
                     if (DKV) {
                         // a block holds 4 consecutive KEYS of one query: lane j of each quad (4 consecutive keys, one block) draws the
-                        // blocks of the quad's queries 8 g4 + 4 h + j, and the quad exchanges the nibbles
+                        // blocks of the quad's queries at_walked(4 g4, h) + j, and the quad exchanges the nibbles
                         unsigned nb = 0;
 #pragma unroll
                         for (int g4 = 0; g4 < 4; ++g4)
-                            nb |= keep_nibble(dk, g, head, w0 + 8 * g4 + 4 * h + (lane & 3), own >> 2) << (4 * g4);
+                            nb |= keep_nibble(dk, g, head, w0 + at_walked(4 * g4, h) + (lane & 3), own >> 2) << (4 * g4);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) keep[e] = (unsigned)__shfl((int)nb, (lane & ~3) + e, 64) >> (lane & 3);
                     } else {
 #pragma unroll
-                        for (int g4 = 0; g4 < 4; ++g4) keep[g4] = keep_nibble(dk, g, head, own, (w0 + 8 * g4 + 4 * h) >> 2);
+                        for (int g4 = 0; g4 < 4; ++g4) keep[g4] = keep_nibble(dk, g, head, own, (w0 + at_walked(4 * g4, h)) >> 2);
                     }
                 }
                 f32x16 pt;                                     // P~ (dK/dV only)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
-                    const float4 x0 = *reinterpret_cast<const float4*>(&aux0[sub * 32 + 8 * g4 + 4 * h]);
-                    const float4 x1 = *reinterpret_cast<const float4*>(&aux1[sub * 32 + 8 * g4 + 4 * h]);
+                    const float4 x0 = *reinterpret_cast<const float4*>(&aux0[sub * 32 + at_walked(4 * g4, h)]);
+                    const float4 x1 = *reinterpret_cast<const float4*>(&aux1[sub * 32 + at_walked(4 * g4, h)]);
                     const float v0[4] = {x0.x, x0.y, x0.z, x0.w}, v1[4] = {x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int r = 4 * g4 + e;
-                        const bool dead = DKV ? (dead_o || w0 + 8 * g4 + 4 * h + e >= N) : (v0[e] != 0.f);
+                        const bool dead = DKV ? (dead_o || w0 + at_walked(r, h) >= N) : (v0[e] != 0.f);
                         const float lse_r = DKV ? v0[e] : lse_o, del_r = DKV ? v1[e] : del_o;
                         const float p = dead ? 0.f : __expf(s[r] * scale - lse_r);
                         float dpv = dp[r], pv = p;
@@ -364,8 +322,6 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
                 }
                 if (sum_delta) continue;
 #pragma unroll
-                // dS and P~ enter their products as hi + lo 16-bit pairs (two MFMAs on one A fragment): rounded once to 16 bits they
-                // carry an error of the size of the RESULT's own rounding -- measured 1.5 x torch's mean and up to 3.3 x its max error
                 for (int sl = 0; sl < 2; ++sl) {
                     V8 dsb, dsl, ptb, ptl;
 #pragma unroll
@@ -377,14 +333,8 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
                     }
 #pragma unroll
                     for (int dt = 0; dt < 2; ++dt) {
-                        const V8 f1 = at_frag_tr<T, V8, V4>(tr1, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h);
-                        acc1[dt] = E::mfma(f1, dsb, acc1[dt]);
-                        acc1[dt] = E::mfma(f1, dsl, acc1[dt]);
-                        if (DKV) {
-                            const V8 f2 = at_frag_tr<T, V8, V4>(tr2, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h);
-                            acc2[dt] = E::mfma(f2, ptb, acc2[dt]);
-                            acc2[dt] = E::mfma(f2, ptl, acc2[dt]);
-                        }
+                        at_mfma_hilo<F16>(acc1[dt], at_frag_tr<F16>(tr1, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h), dsb, dsl);
+                        if (DKV) at_mfma_hilo<F16>(acc2[dt], at_frag_tr<F16>(tr2, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h), ptb, ptl);
                     }
                 }
             }
@@ -396,16 +346,16 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
     }
 
     if (own < N) {
-        T* op = dqkv + (row_base + own) * AT_QKV_LD + head * 64 + (DKV ? BG_D_MODEL : 0);
+        T* op = dqkv + (row_base + own) * QKV_LD + head * 64 + (DKV ? BG_D_MODEL : 0);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int d = dt * 32 + 8 * g4 + 4 * h;
-                *reinterpret_cast<V4*>(op + d) = E::pack4(acc1[dt][4 * g4 + 0] * scale, acc1[dt][4 * g4 + 1] * scale,
-                                                          acc1[dt][4 * g4 + 2] * scale, acc1[dt][4 * g4 + 3] * scale);
+                *reinterpret_cast<typename E::V4*>(op + d) = E::pack4(acc1[dt][4 * g4 + 0] * scale, acc1[dt][4 * g4 + 1] * scale,
+                                                                      acc1[dt][4 * g4 + 2] * scale, acc1[dt][4 * g4 + 3] * scale);
                 if (DKV)
-                    *reinterpret_cast<V4*>(op + BG_D_MODEL + d) =
+                    *reinterpret_cast<typename E::V4*>(op + BG_D_MODEL + d) =
                         E::pack4(acc2[dt][4 * g4 + 0], acc2[dt][4 * g4 + 1], acc2[dt][4 * g4 + 2], acc2[dt][4 * g4 + 3]);
             }
     }
@@ -416,7 +366,8 @@ __global__ __launch_bounds__(256, 2) void at_bwd16_kernel(const void* __restrict
 //   1. K, V (row-major), K^T, Q^T, dO^T (transposed) of the head are staged once.
 //   2. Wave w owns queries 32 w .. 32 w + 31 exactly as the dQ kernel does (S^T = K Q^T, dP^T = V dO^T, both 32-key sub-tiles in
 //      registers), so delta is a sum over the lane's own registers -- no second walk, no workspace -- and dQ^T = K^T dS^T follows.
-//      Same instructions in the same order as the general path: dQ is that path's, bit for bit.
+//      The same arithmetic in the same order as the general path (attn_tile.h's helpers restate its text): dQ is that path's, bit
+//      for bit (asserted).
 //   3. dV and dK sum over the QUERY, which sits on the lane: P~ and then dS cross the LDS once, as hi + lo 16-bit images [key][query]
 //      laid over the K / V / K^T images (dead by then), and wave w, now owning KEYS 32 w .. 32 w + 31, reads them back as the B
 //      operand of dV^T = dO^T P~ and dK^T = Q^T dS (A operand: the transposed dO / Q image, queries in natural order).
@@ -430,7 +381,6 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
     using E = Elem<F16>;
     using T = typename E::T;
     using V8 = typename E::V8;
-    using V4 = typename E::V4;
     static_assert(2 * 64 * AT_PS * 2 <= 2 * AT_RM + AT_TR, "the exchange images fit over K | V | K^T");
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * AT_RM + 3 * AT_TR + 256];
     unsigned char* krm = lds;
@@ -450,27 +400,15 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
     const int b = blockIdx.z, head = blockIdx.y;
     const int own0 = wave * 32, own = own0 + l31, ownc = own < N ? own : N - 1;
     const size_t row_base = (size_t)b * N;
-    const T* qb = qkv + row_base * AT_QKV_LD + head * 64;
+    const T* qb = qkv + row_base * QKV_LD + head * 64;
     const T* dob = dout + row_base * BG_D_MODEL + head * 64;
     const unsigned long long g = dk.first + (unsigned long long)b;
 
     // ---- 1. stage ----
-    for (int idx = tid; idx < 512; idx += 128) {
-        const int row = idx >> 3, c = idx & 7;
-        const size_t gr = (size_t)(row < N ? row : N - 1);
-        const V8 kv = *reinterpret_cast<const V8*>(qb + gr * AT_QKV_LD + BG_D_MODEL + c * 8);
-        const V8 vv = *reinterpret_cast<const V8*>(qb + gr * AT_QKV_LD + 2 * BG_D_MODEL + c * 8);
-        const V8 qv = *reinterpret_cast<const V8*>(qb + gr * AT_QKV_LD + c * 8);
-        const V8 dv = *reinterpret_cast<const V8*>(dob + gr * BG_D_MODEL + c * 8);
-        *reinterpret_cast<V8*>(krm + row * 128 + ((c ^ swz_term(row)) << 4)) = kv;
-        *reinterpret_cast<V8*>(vrm + row * 128 + ((c ^ swz_term(row)) << 4)) = vv;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            ktr[(c * 8 + e) * AT_VS + row] = kv[e];
-            qtr[(c * 8 + e) * AT_VS + row] = qv[e];
-            dotr[(c * 8 + e) * AT_VS + row] = dv[e];
-        }
-    }
+    at_stage<F16, 128, true, true>(qb + BG_D_MODEL, QKV_LD, 0, N, krm, ktr, tid);
+    at_stage<F16, 128, true, false>(qb + 2 * BG_D_MODEL, QKV_LD, 0, N, vrm, nullptr, tid);
+    at_stage<F16, 128, false, true>(qb, QKV_LD, 0, N, nullptr, qtr, tid);
+    at_stage<F16, 128, false, true>(dob, BG_D_MODEL, 0, N, nullptr, dotr, tid);
     if (tid < 64) deadf[tid] = (tid >= N || (key_pad != nullptr && key_pad[row_base + tid] != 0)) ? 1.f : 0.f;
     __syncthreads();
 
@@ -482,11 +420,8 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
         for (int r = 0; r < 16; ++r) { pt[sub][r] = 0.f; ds[sub][r] = 0.f; }
     if (own0 < N) {                                        // wave-uniform
         V8 xf[4], yf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            xf[ks] = *reinterpret_cast<const V8*>(qb + (size_t)ownc * AT_QKV_LD + (ks * 2 + h) * 8);
-            yf[ks] = *reinterpret_cast<const V8*>(dob + (size_t)ownc * BG_D_MODEL + (ks * 2 + h) * 8);
-        }
+        at_row_frags<F16>(qb + (size_t)ownc * QKV_LD, h, xf);
+        at_row_frags<F16>(dob + (size_t)ownc * BG_D_MODEL, h, yf);
         const float lse_o = lse[((size_t)b * BG_N_HEAD + head) * N + ownc];
         f32x16 dpm[2];                                     // masked dP
         float dsum = 0.f;
@@ -497,26 +432,21 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                s = E::mfma(at_frag_rm<V8>(krm, sub * 32 + l31, ks * 2 + h), xf[ks], s);
-                dp = E::mfma(at_frag_rm<V8>(vrm, sub * 32 + l31, ks * 2 + h), yf[ks], dp);
+                s = E::mfma(at_frag_rm<F16>(krm, sub * 32 + l31, ks * 2 + h), xf[ks], s);
+                dp = E::mfma(at_frag_rm<F16>(vrm, sub * 32 + l31, ks * 2 + h), yf[ks], dp);
             }
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 unsigned nib = 0xFu;
-                if (DROP) nib = keep_nibble(dk, g, head, own, (sub * 32 + 8 * g4 + 4 * h) >> 2);
-                const float4 x0 = *reinterpret_cast<const float4*>(&deadf[sub * 32 + 8 * g4 + 4 * h]);
+                if (DROP) nib = keep_nibble(dk, g, head, own, (sub * 32 + at_walked(4 * g4, h)) >> 2);
+                const float4 x0 = *reinterpret_cast<const float4*>(&deadf[sub * 32 + at_walked(4 * g4, h)]);
                 const float v0[4] = {x0.x, x0.y, x0.z, x0.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int r = 4 * g4 + e;
                     const bool dead = v0[e] != 0.f || own >= N;
-                    const float p = dead ? 0.f : __expf(s[r] * scale - lse_o);
-                    float dpv = dp[r], pv = p;
-                    if (DROP) {
-                        const bool kept = (nib >> e) & 1u;
-                        dpv = kept ? dpv * dk.rp : 0.f;
-                        pv = kept ? p * dk.rp : 0.f;
-                    }
+                    float dpv = dp[r], pv;
+                    const float p = at_bwd_elem<DROP>(s[r], scale, lse_o, dead, (nib >> e) & 1u, dk.rp, dpv, pv);
                     dsum += dead ? 0.f : p * dpv;
                     pt[sub][r] = pv;
                     ds[sub][r] = p;                        // P for now
@@ -537,29 +467,13 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
 #pragma unroll
             for (int sl = 0; sl < 2; ++sl) {
                 V8 dsb, dsl;
+                at_split8<F16>(ds[sub], sl, dsb, dsl);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    dsb[e] = (T)ds[sub][8 * sl + e];
-                    dsl[e] = (T)(ds[sub][8 * sl + e] - (float)dsb[e]);
-                }
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const V8 f1 = at_frag_tr<T, V8, V4>(ktr, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h);
-                    acc[dt] = E::mfma(f1, dsb, acc[dt]);
-                    acc[dt] = E::mfma(f1, dsl, acc[dt]);
-                }
+                for (int dt = 0; dt < 2; ++dt)
+                    at_mfma_hilo<F16>(acc[dt], at_frag_tr<F16>(ktr, dt * 32 + l31, sub * 32 + 16 * sl + 4 * h), dsb, dsl);
             }
         }
-        if (own < N) {
-            T* op = dqkv + (row_base + own) * AT_QKV_LD + head * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4)
-                    *reinterpret_cast<V4*>(op + dt * 32 + 8 * g4 + 4 * h) =
-                        E::pack4(acc[dt][4 * g4 + 0] * scale, acc[dt][4 * g4 + 1] * scale, acc[dt][4 * g4 + 2] * scale,
-                                 acc[dt][4 * g4 + 3] * scale);
-        }
+        if (own < N) at_store_acc<F16>(dqkv + (row_base + own) * QKV_LD + head * 64, acc, scale, h);
     }
 
     // ---- 3. P~ (round 0: dV) and dS (round 1: dK) across the LDS; the wave now owns keys 32 w .. 32 w + 31 ----
@@ -570,11 +484,11 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const float v = round == 0 ? pt[sub][r] : ds[sub][r];
-                const T hi = (T)v;
+                const int key = sub * 32 + at_walked(r, h);
+                T hi, lo;
+                at_hilo(round == 0 ? pt[sub][r] : ds[sub][r], hi, lo);
                 img_hi[key * AT_PS + own] = hi;
-                img_lo[key * AT_PS + own] = (T)(v - (float)hi);
+                img_lo[key * AT_PS + own] = lo;
             }
         __syncthreads();
         if (own0 >= N) continue;                           // wave-uniform: no key of this wave exists
@@ -590,27 +504,11 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
             const V8 bh = *reinterpret_cast<const V8*>(img_hi + own * AT_PS + 16 * ks + 8 * h);
             const V8 bl = *reinterpret_cast<const V8*>(img_lo + own * AT_PS + 16 * ks + 8 * h);
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const T* ap = tr + (dt * 32 + l31) * AT_VS + 16 * ks + 8 * h;
-                const V4 lo = *reinterpret_cast<const V4*>(ap);
-                const V4 hi = *reinterpret_cast<const V4*>(ap + 4);
-                V8 a;
-                a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
-                a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
-                acc[dt] = E::mfma(a, bh, acc[dt]);
-                acc[dt] = E::mfma(a, bl, acc[dt]);
-            }
+            for (int dt = 0; dt < 2; ++dt) at_mfma_hilo<F16>(acc[dt], at_frag_tr<F16, 4>(tr, dt * 32 + l31, 16 * ks + 8 * h), bh, bl);
         }
-        if (own < N) {
-            const float f = round == 0 ? 1.0f : scale;
-            T* op = dqkv + (row_base + own) * AT_QKV_LD + head * 64 + (round == 0 ? 2 * BG_D_MODEL : BG_D_MODEL);
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4)
-                    *reinterpret_cast<V4*>(op + dt * 32 + 8 * g4 + 4 * h) =
-                        E::pack4(acc[dt][4 * g4 + 0] * f, acc[dt][4 * g4 + 1] * f, acc[dt][4 * g4 + 2] * f, acc[dt][4 * g4 + 3] * f);
-        }
+        if (own < N)
+            at_store_acc<F16>(dqkv + (row_base + own) * QKV_LD + head * 64 + (round == 0 ? 2 * BG_D_MODEL : BG_D_MODEL), acc,
+                              round == 0 ? 1.0f : scale, h);
     }
 }
 
@@ -619,12 +517,6 @@ __global__ __launch_bounds__(128) void at_bwd16_short_kernel(const void* __restr
 // results, every dot product and sum accumulated in fp64 (v_fma_f64, a fixed order) and rounded once: the parity mode's error is the
 // rounding of P, dS and the results themselves, not the length of a chain.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void at_wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 template <bool DROP>
 __global__ __launch_bounds__(256) void at_fwd32_kernel(const float* __restrict__ qkv, const uint8_t* __restrict__ key_pad,
                                                        float* __restrict__ out, float* __restrict__ lse, int N, float scale, DropKey dk) {
@@ -635,8 +527,8 @@ __global__ __launch_bounds__(256) void at_fwd32_kernel(const float* __restrict__
     float* p = at_dyn + (size_t)wave * N;
     const size_t row_base = (size_t)b * N;
     if (q >= N) return;                                // no block-level barriers below
-    const float* base = qkv + row_base * AT_QKV_LD + head * 64;
-    const float* qp = base + (size_t)q * AT_QKV_LD;
+    const float* base = qkv + row_base * QKV_LD + head * 64;
+    const float* qp = base + (size_t)q * QKV_LD;
     const unsigned long long g = dk.first + (unsigned long long)b;
     float qv[64];
 #pragma unroll
@@ -645,7 +537,7 @@ __global__ __launch_bounds__(256) void at_fwd32_kernel(const float* __restrict__
     for (int j = lane; j < N; j += 64) {
         float sc = -INFINITY;
         if (!(key_pad != nullptr && key_pad[row_base + j] != 0)) {
-            const float* kp = base + (size_t)j * AT_QKV_LD + BG_D_MODEL;
+            const float* kp = base + (size_t)j * QKV_LD + BG_D_MODEL;
             double acc = 0.0;
 #pragma unroll
             for (int d = 0; d < 64; ++d) acc = fma((double)qv[d], (double)kp[d], acc);
@@ -671,9 +563,9 @@ __global__ __launch_bounds__(256) void at_fwd32_kernel(const float* __restrict__
     int j = 0;
     for (; j + 4 <= N; j += 4) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] = fma((double)p[j + u], (double)vb[(size_t)(j + u) * AT_QKV_LD], a[u]);
+        for (int u = 0; u < 4; ++u) a[u] = fma((double)p[j + u], (double)vb[(size_t)(j + u) * QKV_LD], a[u]);
     }
-    for (int u = 0; j + u < N; ++u) a[u] = fma((double)p[j + u], (double)vb[(size_t)(j + u) * AT_QKV_LD], a[u]);
+    for (int u = 0; j + u < N; ++u) a[u] = fma((double)p[j + u], (double)vb[(size_t)(j + u) * QKV_LD], a[u]);
     const float acc = (float)((a[0] + a[1]) + (a[2] + a[3]));
     out[(row_base + q) * BG_D_MODEL + head * 64 + lane] = l > 0.f ? (DROP ? acc * dk.rp : acc) / l : 0.f;
     if (lane == 0) lse[((size_t)b * BG_N_HEAD + head) * N + q] = l > 0.f ? m_use + logf(l) : 0.f;
@@ -693,7 +585,7 @@ __global__ __launch_bounds__(256) void at_bwd32_kernel(const float* __restrict__
     float* pt = ds + N;
     const size_t row_base = (size_t)b * N;
     if (own >= N) return;                              // no block-level barriers below
-    const float* qb = qkv + row_base * AT_QKV_LD + head * 64;
+    const float* qb = qkv + row_base * QKV_LD + head * 64;
     const float* dob = dout + row_base * BG_D_MODEL + head * 64;
     // workspace: delta | row maximum | row sum, [B, 12, N] each, written by the dQ kernel and read by the dK/dV kernel.  The fp32
     // kernels normalise as torch does, P = exp(S - max) / sum: lse rounded to fp32 (|lse| up to ~8) would put an error of several
@@ -703,14 +595,14 @@ __global__ __launch_bounds__(256) void at_bwd32_kernel(const float* __restrict__
     float* max_b = del_b + plane;
     float* sum_b = del_b + 2 * plane;
     const unsigned long long g = dk.first + (unsigned long long)b;
-    float* op = dqkv + (row_base + own) * AT_QKV_LD + head * 64 + lane;
+    float* op = dqkv + (row_base + own) * QKV_LD + head * 64 + lane;
     if (DKV && key_pad != nullptr && key_pad[row_base + own] != 0) {      // wave-uniform: a padded key has P = 0 in every row
         op[BG_D_MODEL] = 0.f;
         op[2 * BG_D_MODEL] = 0.f;
         return;
     }
-    const float* xp = (DKV ? qb + BG_D_MODEL : qb) + (size_t)own * AT_QKV_LD;
-    const float* yp = DKV ? qb + 2 * BG_D_MODEL + (size_t)own * AT_QKV_LD : dob + (size_t)own * BG_D_MODEL;
+    const float* xp = (DKV ? qb + BG_D_MODEL : qb) + (size_t)own * QKV_LD;
+    const float* yp = DKV ? qb + 2 * BG_D_MODEL + (size_t)own * QKV_LD : dob + (size_t)own * BG_D_MODEL;
     float xv[64], yv[64];
 #pragma unroll
     for (int d = 0; d < 64; ++d) { xv[d] = xp[d]; yv[d] = yp[d]; }
@@ -719,8 +611,8 @@ __global__ __launch_bounds__(256) void at_bwd32_kernel(const float* __restrict__
         const int qi = DKV ? w : own, kj = DKV ? own : w;
         float dsv = 0.f, ptv = DKV ? 0.f : -INFINITY;  // dQ: pt carries the score first (-inf = padded key)
         if (!(!DKV && key_pad != nullptr && key_pad[row_base + w] != 0)) {
-            const float* a1 = (DKV ? qb : qb + BG_D_MODEL) + (size_t)w * AT_QKV_LD;
-            const float* a2 = DKV ? dob + (size_t)w * BG_D_MODEL : qb + 2 * BG_D_MODEL + (size_t)w * AT_QKV_LD;
+            const float* a1 = (DKV ? qb : qb + BG_D_MODEL) + (size_t)w * QKV_LD;
+            const float* a2 = DKV ? dob + (size_t)w * BG_D_MODEL : qb + 2 * BG_D_MODEL + (size_t)w * QKV_LD;
             double sacc = 0.0, dacc = 0.0;
 #pragma unroll
             for (int d = 0; d < 64; ++d) sacc = fma((double)xv[d], (double)a1[d], sacc);
@@ -775,12 +667,12 @@ __global__ __launch_bounds__(256) void at_bwd32_kernel(const float* __restrict__
     for (; w + 4 <= N; w += 4) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            a[u] = fma((double)ds[w + u], (double)m1[(size_t)(w + u) * AT_QKV_LD], a[u]);
+            a[u] = fma((double)ds[w + u], (double)m1[(size_t)(w + u) * QKV_LD], a[u]);
             if (DKV) c[u] = fma((double)pt[w + u], (double)m2[(size_t)(w + u) * BG_D_MODEL], c[u]);
         }
     }
     for (int u = 0; w + u < N; ++u) {
-        a[u] = fma((double)ds[w + u], (double)m1[(size_t)(w + u) * AT_QKV_LD], a[u]);
+        a[u] = fma((double)ds[w + u], (double)m1[(size_t)(w + u) * QKV_LD], a[u]);
         if (DKV) c[u] = fma((double)pt[w + u], (double)m2[(size_t)(w + u) * BG_D_MODEL], c[u]);
     }
     const float r1 = (float)(((a[0] + a[1]) + (a[2] + a[3])) * (double)scale);
@@ -855,11 +747,9 @@ extern "C" int bg_attn_train_fwd(const void* qkv, const uint8_t* key_pad, void* 
         return launch_status("attn_train_fwd_f32");
     }
     const dim3 grid((N + 127) / 128, BG_N_HEAD, B);
-    const bool f16 = dtype == BG_F16;
-    if (f16 && drop) hipLaunchKernelGGL((at_fwd16_kernel<true, true>), grid, dim3(256), 0, s, qkv, key_pad, out, lse, N, scale, dk);
-    else if (f16) hipLaunchKernelGGL((at_fwd16_kernel<true, false>), grid, dim3(256), 0, s, qkv, key_pad, out, lse, N, scale, dk);
-    else if (drop) hipLaunchKernelGGL((at_fwd16_kernel<false, true>), grid, dim3(256), 0, s, qkv, key_pad, out, lse, N, scale, dk);
-    else hipLaunchKernelGGL((at_fwd16_kernel<false, false>), grid, dim3(256), 0, s, qkv, key_pad, out, lse, N, scale, dk);
+    with_bools(dtype == BG_F16, drop, [&](auto F16, auto DROP) {
+        hipLaunchKernelGGL((at_fwd16_kernel<F16(), DROP()>), grid, dim3(256), 0, s, qkv, key_pad, out, lse, N, scale, dk);
+    });
     return launch_status("attn_train_fwd16");
 }
 
@@ -867,13 +757,6 @@ extern "C" size_t bg_attn_bwd_workspace_bytes(int B, int N, int dtype) {
     if (B <= 0 || N < 1 || !(dtype == BG_BF16 || dtype == BG_F16 || dtype == BG_F32)) return 0;
     // delta [B, 12, N]; BG_F32: + row maximum and row sum
     return (((size_t)B * BG_N_HEAD * N * sizeof(float) * (dtype == BG_F32 ? 3 : 1)) + 255) & ~(size_t)255;
-}
-
-template <bool F16, bool DROP>
-static void at_launch_bwd16(const dim3& grid, hipStream_t s, const void* qkv, const uint8_t* key_pad, const float* lse, float* delta,
-                            const void* dout, void* dqkv, int N, float scale, const DropKey& dk) {
-    hipLaunchKernelGGL((at_bwd16_kernel<F16, DROP, false>), grid, dim3(256), 0, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
-    hipLaunchKernelGGL((at_bwd16_kernel<F16, DROP, true>), grid, dim3(256), 0, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
 }
 
 template <bool DROP>
@@ -918,21 +801,16 @@ extern "C" int bg_attn_bwd(const void* qkv, const uint8_t* key_pad, const float*
     }
     if (variant == BG_ATTN_BWD_SHORT || (variant == BG_ATTN_BWD_AUTO && N <= AT_SHORT_AUTO_N)) {
         const dim3 sgrid(1, BG_N_HEAD, B);
-        const bool f16 = dtype == BG_F16;
-        if (f16 && drop) hipLaunchKernelGGL((at_bwd16_short_kernel<true, true>), sgrid, dim3(128), 0, s, qkv, key_pad, lse, dout, dqkv, N, scale, dk);
-        else if (f16) hipLaunchKernelGGL((at_bwd16_short_kernel<true, false>), sgrid, dim3(128), 0, s, qkv, key_pad, lse, dout, dqkv, N, scale, dk);
-        else if (drop) hipLaunchKernelGGL((at_bwd16_short_kernel<false, true>), sgrid, dim3(128), 0, s, qkv, key_pad, lse, dout, dqkv, N, scale, dk);
-        else hipLaunchKernelGGL((at_bwd16_short_kernel<false, false>), sgrid, dim3(128), 0, s, qkv, key_pad, lse, dout, dqkv, N, scale, dk);
+        with_bools(dtype == BG_F16, drop, [&](auto F16, auto DROP) {
+            hipLaunchKernelGGL((at_bwd16_short_kernel<F16(), DROP()>), sgrid, dim3(128), 0, s, qkv, key_pad, lse, dout, dqkv, N, scale, dk);
+        });
         return launch_status("attn_bwd16_short");
     }
     const dim3 grid((N + 127) / 128, BG_N_HEAD, B);
-    if (dtype == BG_F16) {
-        if (drop) at_launch_bwd16<true, true>(grid, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
-        else at_launch_bwd16<true, false>(grid, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
-    } else {
-        if (drop) at_launch_bwd16<false, true>(grid, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
-        else at_launch_bwd16<false, false>(grid, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
-    }
+    with_bools(dtype == BG_F16, drop, [&](auto F16, auto DROP) {
+        hipLaunchKernelGGL((at_bwd16_kernel<F16(), DROP(), false>), grid, dim3(256), 0, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
+        hipLaunchKernelGGL((at_bwd16_kernel<F16(), DROP(), true>), grid, dim3(256), 0, s, qkv, key_pad, lse, delta, dout, dqkv, N, scale, dk);
+    });
     return launch_status("attn_bwd16");
 }
 

@@ -1,6 +1,6 @@
 // Pieces shared by the 16-bit MFMA kernels -- gemm_16bit.hip (128 x 128 persistent + generic tiles), gemm_p256.hip (256 x 256
 // persistent, 8-phase K loop), gemm_split.hip (pipelined split-residual epilogue), qkv_attn.hip (fused QKV + attention),
-// ffn_fused.hip (FFN1 + FFN2 in one launch); attn.hip takes the element types and the swizzle from here.  These kernels produce the same bits for the same
+// ffn_fused.hip (FFN1 + FFN2 in one launch); attn.hip / attn_train.hip take the types and the swizzle through attn_tile.h.  These kernels produce the same bits for the same
 // work (the tests assert it kernel against kernel), and what makes them do so is defined ONCE, in this file: the element types, the
 // LDS-DMA instruction, the 16-byte XOR swizzle, the split-residual octet, the LayerNorm-fold row coefficients, the 128 x 128 tile
 // walk and the accumulator-to-patch write.  Every helper is forceinline and takes lane / row values as parameters: several kernels

@@ -413,3 +413,16 @@ def test_shared_device_steps_are_defined_once():
     sq = "(v[0]*v[0]+v[1]*v[1])+(v[2]*v[2]+v[3]*v[3])"
     with_sq = sorted(f for f, t in texts.items() if sq in re.sub(r"\s+", "", t))
     assert with_sq == ["gemm16.h"], with_sq
+    # (c) the attention kernels' tile steps (csrc/attn_tile.h).  The transposing LDS write: at_stage there, and attn.hip's
+    # attn16_kernel, the named exception (through a helper its instruction stream changed, and it is on the product path).  The
+    # online-softmax rescale has no shared definition -- every kernel that has it is a named exception, ONE copy each: qkv_attn.hip
+    # (hand-scheduled), attn.hip's attn16_kernel and attn_train.hip's at_fwd16_kernel (behind a helper both came out as another
+    # instruction stream, and the dropout forward measured slower: DESIGN.md section 4)
+    squeezed = {f: re.sub(r"\s+", "", t) for f, t in texts.items()}
+    tr_write = re.compile(r"\*\w+\+row\]=\w+\[e\]")
+    with_tr_write = sorted(f for f, t in squeezed.items() if tr_write.search(t))
+    assert with_tr_write == ["attn.hip", "attn_tile.h"], with_tr_write
+    assert all(len(tr_write.findall(squeezed[f])) == 1 for f in with_tr_write)
+    with_rescale = sorted(f for f, t in squeezed.items() if "__expf(m_run-m_use)" in t)
+    assert with_rescale == ["attn.hip", "attn_train.hip", "qkv_attn.hip"], with_rescale
+    assert all(squeezed[f].count("__expf(m_run-m_use)") == 1 for f in with_rescale)

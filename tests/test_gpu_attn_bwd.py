@@ -30,6 +30,7 @@ import brepgen_amd as bga
 from brepgen_amd import optim  # noqa: F401
 from tests import attn_bwd_restate as R
 from tests import attn_train_ops as ops
+from tests import hip_ops
 from tests.guarded import guarded
 
 pytestmark = pytest.mark.gpu
@@ -201,6 +202,36 @@ def test_bitwise_invariants(dtype, N, variant):
     assert torch.equal(o3.view(torch.uint8), out[2:].view(torch.uint8)) and torch.equal(d3.view(torch.uint8), dqkv[2:].view(torch.uint8))
     o4, _, _ = _kernel(sub, dtype, p, seed, draw, first=0)                                            # ... and not with another one
     assert not torch.equal(o4.view(torch.uint8), out[2:].view(torch.uint8))
+
+
+def _same_bytes(a, b):
+    return torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("N", [5, 33, 64])
+@pytest.mark.parametrize("dtype", HALF, ids=["fp16", "bf16"])
+def test_short_and_general_backward_agree_on_dq_bit_for_bit(dtype, N, p):
+    """The one-launch kernel forms dQ by the general path's arithmetic in the same order (its helpers in csrc/attn_tile.h restate the
+    general kernel's own text): the same bytes, with and without dropout, with an all-padded sample in the batch.  (dK and dV are
+    rounded through LDS images there: not compared.)"""
+    case = ops.make_case(3, N, "one_empty", 7000 + N, dtype)
+    short = _kernel(case, dtype, p, 99, 4, variant=SHORT)[2]
+    general = _kernel(case, dtype, p, 99, 4, variant=GENERAL)[2]
+    assert _same_bytes(short[..., :768], general[..., :768])
+
+
+@pytest.mark.parametrize("N", [5, 33, 64])
+@pytest.mark.parametrize("dtype", HALF, ids=["fp16", "bf16"])
+def test_training_forward_equals_the_inference_kernel_bit_for_bit(dtype, N):
+    """bg_attn_train_fwd with scale 1 and no dropout is bg_attn_fwd (which expects q pre-scaled): the same bytes of `out`.  N <= 64:
+    longer sequences take attn16_long_kernel, whose deferred maximum differs by design."""
+    B = 3
+    case = ops.make_case(B, N, "tail", 8000 + N, dtype)
+    qkv = case["qkv_t"].cuda().reshape(B * N, 2304)
+    kp = _dev(case["key_pad"].astype(np.uint8))
+    out_train, _ = ops.train_fwd(qkv, kp, B, N, 1.0, 0.0)
+    assert _same_bytes(out_train, hip_ops.attention(qkv, kp, B, N))
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "fp16", "bf16"])
