@@ -12,6 +12,7 @@ Drop-in for the reference's call surface on that path only:
     dedup_cads / unique_items (data_process/deduplicate_*.py)       (deduplicate.py) -> bg_points_sha256 / bg_digest_group_keys / bg_first_occurrence
     optim.AdamW / optim.GradScaler / optim.clip_grad_norm_ (trainer.py's update) (optim.py) -> bg_mt_grad_stats / bg_mt_adamw_step / bg_optim_finish
     nn.MultiheadAttention in net.train() (attention core, dropout, backward) (attention.py) -> bg_attn_train_fwd / bg_attn_bwd
+    nn.Linear of the encoder layers under autocast (forward, dX, dW + db) (linear.py) -> bg_weight_cast / bg_gemm_ex_fwd / bg_linear_wgrad
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from . import optim  # noqa: F401
@@ -44,6 +45,10 @@ __all__ += list(_DEDUPLICATE)
 # the attention core for training: forward with dropout + backward on the device (attention.py)
 _ATTENTION = ("self_attention", "MultiheadSelfAttention", "use_device_attention")
 __all__ += list(_ATTENTION)
+# the Linear layers of an encoder layer, forward and backward on the device (linear.py; the op itself is brepgen_amd.linear.linear:
+# the package attribute `linear` is the submodule)
+_LINEAR = ("DeviceLinear", "use_device_linear")
+__all__ += list(_LINEAR)
 
 
 def __getattr__(name):
@@ -65,4 +70,7 @@ def __getattr__(name):
     if name in _ATTENTION:
         from . import attention
         return getattr(attention, name)
+    if name in _LINEAR:
+        from . import linear
+        return getattr(linear, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -190,6 +190,11 @@ _SIGNATURES = {
     "bg_attn_bwd": (C.c_int, [vp, u8p, fp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_ulonglong, C.c_uint,
                               C.c_longlong, C.c_int, vp, C.c_size_t, vp]),
     "bg_attn_dropout_mask": (C.c_int, [u8p, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_uint, C.c_longlong, vp]),
+    "bg_linear_wgrad": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                  C.c_size_t, vp]),
+    "bg_linear_wgrad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bg_linear_wgrad_split": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "bg_weight_cast": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -186,6 +186,33 @@ int bg_attn_bwd(const void* qkv, const uint8_t* key_pad, const float* lse, const
 int bg_attn_dropout_mask(uint8_t* mask, int B, int N, double dropout_p, unsigned long long seed, unsigned draw_id, long long first_sample,
                          bg_stream_t stream);
 
+/* ---- the Linear layers' backward (csrc/linear_bwd.hip): what torch's autograd does for the four nn.Linear of an encoder layer
+ * (network.py:1076-1078) under autocast.  y = x W^T + b and dX = dY W run on bg_gemm_ex_fwd (dX: a = dY, w = W^T as bg_weight_cast
+ * writes it); the weight and bias gradients are the product below. */
+
+/* dw [N, K] (nn.Linear layout) = sum_m dy[m, n] x[m, k] and db [N] = sum_m dy[m, n] (db may be NULL) in ONE launch (two with a
+ * split).  dy [M, N] and x [M, K] are 16-bit of `dtype` (BG_BF16 | BG_F16), row-major with row strides ld_dy >= N, ld_x >= K in
+ * elements, multiples of 8; all bases 16-byte aligned.  out_dtype: BG_F32 (fp32 master parameters: the fp32 sum is never rounded to
+ * 16 bits) or `dtype`.  N % 128 == 0 and K % 128 == 0, else BG_E_SHAPE; M >= 1; M == 0 writes zeros to dw / db.  Only rows < M and
+ * columns < N (K) of dy (x) are read.
+ * A workgroup owns one 128 x 128 tile of dw and one contiguous slice of the M rows, walked in steps of 32 rows; slice s of S covers
+ * rows [s R, min(M, (s + 1) R)), R = 32 * ceil(ceil(M / 32) / S).  split = S: 0 = auto (bg_linear_wgrad_split), or 1 .. 64; an S that
+ * leaves a slice empty is BG_E_ARG.  S == 1 writes dw / db directly and needs no workspace (NULL is fine); S > 1 writes fp32 partials
+ * [S][N][K] then [S][N] to the workspace and a second kernel adds them in index order.  A workspace smaller than
+ * bg_linear_wgrad_workspace_bytes is BG_E_ARG.  No atomics, one writer per element, fixed summation order: two calls give the same
+ * bits, and with fp32 output row n of dw depends on column n of dy alone.  A non-finite dy[m, n] makes dw[n, :] and db[n] non-finite
+ * (a GradScaler's found_inf trips) and leaves the other rows finite. */
+int bg_linear_wgrad(const void* dy, int ld_dy, const void* x, int ld_x, void* dw, void* db, int M, int N, int K, int dtype,
+                    int out_dtype, int split, void* workspace, size_t workspace_bytes, bg_stream_t stream);
+/* 0 for split == 1 (or an auto split that resolves to 1), else 4 * S * N * (K + 1) rounded up to 256 bytes; 0 for rejected arguments. */
+size_t bg_linear_wgrad_workspace_bytes(int M, int N, int K, int split);
+/* host-side plan, no device call: the S that split = 0 resolves to (1 for rejected arguments) */
+int bg_linear_wgrad_split(int M, int N, int K);
+/* src [R, C] (fp32, or 16-bit of `dtype`) -> dst [R, C] and / or dst_t [C, R], both 16-bit of `dtype` (BG_BF16 | BG_F16, round to
+ * nearest even): autocast's per-call weight cast, and the W^T the data-gradient GEMM takes as its w.  Either output may be NULL, not
+ * both.  R % 64 == 0, C % 64 == 0; dense, 16-byte aligned.  One launch: 64 x 64 tiles transposed through LDS. */
+int bg_weight_cast(const void* src, int src_dtype, int R, int C, void* dst, void* dst_t, int dtype, bg_stream_t stream);
+
 /* QKV projection with the LayerNorm fold + self-attention in ONE launch (csrc/qkv_attn.hip): sequences of an even length
  * N <= 64, all B of them equally long; key_pad (may be NULL) as bg_attn_fwd's.  x_hi [B*N, 768] raw 16-bit rows, w_qkv [2304, 768] /
  * bias / colsum as bg_gemm_ex_fwd's fold operands, stats_in [12][B*N][2] the row statistics partials of x; out [B*N, 768] = what
