@@ -13,6 +13,7 @@ Drop-in for the reference's call surface on that path only:
     optim.AdamW / optim.GradScaler / optim.clip_grad_norm_ (trainer.py's update) (optim.py) -> bg_mt_grad_stats / bg_mt_adamw_step / bg_optim_finish
     nn.MultiheadAttention in net.train() (attention core, dropout, backward) (attention.py) -> bg_attn_train_fwd / bg_attn_bwd
     nn.Linear of the encoder layers under autocast (forward, dX, dW + db) (linear.py) -> bg_weight_cast / bg_gemm_ex_fwd / bg_linear_wgrad
+    nn.LayerNorm, ReLU, nn.Dropout and the residual adds of the encoder layers in net.train() (layer.py) -> bg_ln_train_fwd / bg_ln_bwd / bg_dropout_add_fwd / bg_relu_dropout_fwd
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from . import optim  # noqa: F401
@@ -49,6 +50,9 @@ __all__ += list(_ATTENTION)
 # the package attribute `linear` is the submodule)
 _LINEAR = ("DeviceLinear", "use_device_linear")
 __all__ += list(_LINEAR)
+# the rest of an encoder layer in training: LayerNorm forward / backward, dropout + residual add, ReLU + dropout (layer.py)
+_LAYER = ("layer_norm", "dropout_add", "relu_dropout", "DeviceLayerNorm", "DeviceEncoderLayer", "use_device_layer")
+__all__ += list(_LAYER)
 
 
 def __getattr__(name):
@@ -73,4 +77,7 @@ def __getattr__(name):
     if name in _LINEAR:
         from . import linear
         return getattr(linear, name)
+    if name in _LAYER:
+        from . import layer
+        return getattr(layer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -195,6 +195,17 @@ _SIGNATURES = {
     "bg_linear_wgrad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bg_linear_wgrad_split": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "bg_weight_cast": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "bg_ln_train_fwd": (C.c_int, [vp, C.c_int, fp, fp, vp, C.c_int, fp, C.c_int, C.c_float, vp]),
+    "bg_ln_bwd_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "bg_ln_bwd": (C.c_int, [vp, C.c_int, vp, C.c_int, fp, fp, vp, vp, fp, fp, C.c_int, vp, C.c_size_t, vp]),
+    "bg_dropout_add_fwd": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_uint,
+                                     C.c_int, C.c_longlong, vp]),
+    "bg_dropout_bwd": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_uint, C.c_int,
+                                 C.c_longlong, vp]),
+    "bg_relu_dropout_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_uint, C.c_int,
+                                      C.c_longlong, vp]),
+    "bg_relu_dropout_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp]),
+    "bg_dropout_mask": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_uint, C.c_int, C.c_longlong, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -2,7 +2,8 @@
 // mesh_sample.hip: bg_mesh_sample, vae_loss.hip: bg_vae_posterior).  Every user keys the generator with the run's seed and builds its counter from GLOBAL indices plus a
 // 16-bit domain tag in the top half-word of word 3, so no two users ever share a counter.  oracle/philox.py restates it in numpy.
 // Tags in use: 0xB9E5 bg_philox_randn / bg_vae_posterior, 0x5A3D bg_mesh_sample, 0xDA7A bg_batch_plan, 0xDA7B bg_points_rotate_normalize,
-// 0xAD70 the attention dropout mask (attn_train.hip: bg_attn_train_fwd / bg_attn_bwd / bg_attn_dropout_mask).
+// 0xAD70 the attention dropout mask (attn_train.hip: bg_attn_train_fwd / bg_attn_bwd / bg_attn_dropout_mask), 0xD409 the elementwise
+// dropout masks of an encoder layer (layer_train.hip: bg_dropout_add_fwd / bg_dropout_bwd / bg_relu_dropout_fwd / bg_dropout_mask).
 #pragma once
 #include "bg_common.h"
 

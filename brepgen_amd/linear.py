@@ -9,8 +9,9 @@ csrc/linear_bwd.hip.
 
 The trainers run under torch.autocast with fp32 master parameters: x arrives (or is cast, as autocast would) in fp16 / bf16, the
 weight is cast per call by one launch, y and dX come out in x's dtype, and dW / db are written in fp32 straight from the fp32
-accumulators (torch's autocast rounds dW to 16 bits and casts it back).  An fp32 product is not provided.  LayerNorm, ReLU, dropout
-and the embed MLPs of the denoisers (first Linear K = 6 / 12 / 48, output Linear N = 3 .. 18: no multiple of 128) stay torch.
+accumulators (torch's autocast rounds dW to 16 bits and casts it back).  An fp32 product is not provided.  LayerNorm, ReLU and
+dropout are layer.py's (layer.use_device_layer); the embed MLPs of the denoisers (first Linear K = 6 / 12 / 48, output Linear
+N = 3 .. 18: no multiple of 128) stay torch.
 """
 import torch
 import torch.nn as nn

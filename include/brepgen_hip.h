@@ -213,6 +213,69 @@ int bg_linear_wgrad_split(int M, int N, int K);
  * both.  R % 64 == 0, C % 64 == 0; dense, 16-byte aligned.  One launch: 64 x 64 tiles transposed through LDS. */
 int bg_weight_cast(const void* src, int src_dtype, int R, int C, void* dst, void* dst_t, int dtype, bg_stream_t stream);
 
+/* ---- the glue of an encoder layer in TRAINING (csrc/layer_train.hip): what nn.TransformerEncoderLayer(768, 12, 1024, dropout,
+ * norm_first=True) in net.train() does between the attention core and the Linear products above -- LayerNorm forward and backward,
+ * dropout + residual add, ReLU + dropout.  Rows are dense, [M, C] row-major, all bases 16-byte aligned (stats: 8).  Nothing is
+ * allocated, no atomics: every output element has one writer and a fixed summation order, so two calls give the same bits.  M == 0
+ * returns 0 without a launch (bg_ln_bwd: see there).  16-bit data moves 16 bytes per lane; grids are capped at 2048 workgroups and
+ * stride over the rest.
+ *
+ * LayerNorm over 768 columns.  x is the residual stream, BG_F32 / BG_F16 / BG_BF16; y (and dy) is in y_dtype: any of the three for
+ * an fp32 x, x's own dtype or BG_F32 for a 16-bit x (BG_E_DTYPE otherwise).  gamma / beta fp32 [768].  A half-wave of 32 lanes owns a
+ * row; lane l holds the 8-column chunks l, l + 32, l + 64.  Every row sum adds a chunk's 8 values pairwise, the lane's three chunks in
+ * order, then the 32 lanes by a butterfly (offsets 16, 8, 4, 2, 1). */
+
+/* y = (x - mean) * rstd * gamma + beta, rounded ONCE from the fp32 result to y_dtype (autocast's fp32 LayerNorm plus the cast that
+ * follows it, in one pass), and stats fp32 [M, 2] = (mean, rstd) per row.  Two passes over the row held in registers: mean = sum / 768,
+ * then var = (sum of (x - mean)^2) / 768, rstd = 1 / sqrtf(var + eps) -- rows with |mean| >> std keep their variance, a constant row
+ * has var = 0 exactly and y = beta. */
+int bg_ln_train_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype, float* stats, int M,
+                    float eps, bg_stream_t stream);
+/* Workspace of bg_ln_bwd when dgamma / dbeta are asked for: G * 1536 doubles, G = min(ceil(M / (8 R)), 2048) workgroups,
+ * R = min(max(ceil(M / 8192), 4), 64) rows per fp32 chain.  0 for M <= 0. */
+size_t bg_ln_bwd_workspace_bytes(int M);
+/* Reads dy [M, 768] (y_dtype), x and stats as bg_ln_train_fwd left them, gamma, and dskip [M, 768] (x_dtype; may be NULL): the
+ * gradient that arrives over the residual connection, added in the same pass.  Writes dx [M, 768] in x_dtype, every element:
+ *     xhat = (x - mean) * rstd;  g = gamma * dy;  dx = rstd * ((g - mean_c(g)) - xhat * mean_c(g * xhat)) + dskip
+ * (mean_c: the row sum above / 768; `+ dskip` is `+ 0.0f` for a NULL dskip, so a zero dskip and none give the same bits).
+ * dgamma [768] = sum_m dy * xhat and dbeta [768] = sum_m dy, fp32; both NULL = not computed (no workspace needed), one NULL is
+ * BG_E_ARG.  Summation order: workgroup w takes the row chunks w, w + G, ...; in chunk c half-wave s adds rows c * 8 R + 8 i + s,
+ * i = 0 .. R - 1, into an fp32 chain per column; the eight chains of a chunk are added in order of s, in fp64, into the workgroup's
+ * fp64 sum, which goes to workspace[w][1536] (dgamma | dbeta); a second kernel adds the G partials of a column in fp64: 32
+ * contiguous groups of ceil(G / 32) in index order, then the 32 group sums in order, rounded once to fp32.  A workspace smaller than
+ * bg_ln_bwd_workspace_bytes(M) is BG_E_ARG; nothing beyond that size is written.  M == 0 with non-NULL dgamma / dbeta writes zeros.
+ * A row of dx depends on its own row alone and a column of dgamma / dbeta on its own column alone: a non-finite dy[m, c] makes
+ * dx[m, :], dgamma[c] and dbeta[c] non-finite (a GradScaler's found_inf trips) and nothing else. */
+int bg_ln_bwd(const void* dy, int y_dtype, const void* x, int x_dtype, const float* stats, const float* gamma, const void* dskip,
+              void* dx, float* dgamma, float* dbeta, int M, void* workspace, size_t workspace_bytes, bg_stream_t stream);
+
+/* Elementwise dropout.  Rows are sequence-first: row r of [M, C] is token n = r / B of sample b = r % B (M % B == 0), global sample
+ * g = first_sample + b.  The keep mask is a pure function of (seed, draw_id, site, n, g, column): one Philox4x32-10 block, key = seed,
+ * counter = (n * (C / 8) + column_block, low 32 bits of g, draw_id, 0xD4090000 | site << 12 | bits 32..43 of g), serves the 8 columns
+ * 8 column_block .. 8 column_block + 7; element j uses half-word j & 1 (low half first) of word j >> 1 and is KEPT iff that half-word
+ * >= floor(p * 65536) (formed in double); kept values are multiplied by rp = float(1 / (1 - p)).  site 0 .. 3 tells the dropouts of a
+ * layer apart (1 = dropout1, 2 = the FFN dropout, 3 = dropout2).  C % 8 == 0, M * C / 8 < 2^32, 0 <= p < 1,
+ * first_sample + B <= 2^44.  A rank that owns samples [lo, hi) of a sharded batch passes first_sample = lo, B = hi - lo and gets its
+ * rows of the single-GPU mask.  floor(p * 65536) == 0 (p == 0 in particular) runs kernels compiled without the generator. */
+
+/* out = skip + keep * rp * branch.  branch is 16-bit (branch_dtype); skip and out are in stream_dtype = BG_F32 or branch_dtype.
+ * Kept: float(skip) + float(branch) * rp in fp32, rounded once; dropped: skip's value.  out may be skip (in place). */
+int bg_dropout_add_fwd(const void* branch, int branch_dtype, const void* skip, void* out, int stream_dtype, int M, int C, int B,
+                       double p, unsigned long long seed, unsigned draw_id, int site, long long first_sample, bg_stream_t stream);
+/* dbranch (branch_dtype) = keep ? float(dout) * rp : 0, from the same key; dout is in stream_dtype.  (The gradient of skip is dout.) */
+int bg_dropout_bwd(const void* dout, int stream_dtype, void* dbranch, int branch_dtype, int M, int C, int B, double p,
+                   unsigned long long seed, unsigned draw_id, int site, long long first_sample, bg_stream_t stream);
+/* h = (keep && x > 0) ? round(float(x) * rp) : 0, x and h 16-bit of `dtype`.  rp >= 1: a kept positive x never rounds to 0, so h > 0
+ * marks exactly the elements whose gradient passes.  A NaN in a kept element propagates; a DROPPED element is 0 whatever x holds
+ * (torch's relu-then-dropout writes NaN * 0 = NaN there). */
+int bg_relu_dropout_fwd(const void* x, void* h, int dtype, int M, int C, int B, double p, unsigned long long seed, unsigned draw_id,
+                        int site, long long first_sample, bg_stream_t stream);
+/* dx = (h > 0) ? round(float(dh) * rp) : 0 from the saved h: no mask is regenerated, no key is needed. */
+int bg_relu_dropout_bwd(const void* h, const void* dh, void* dx, int dtype, int M, int C, double p, bg_stream_t stream);
+/* The keep mask itself, uint8 [M, C] (1 = kept; 8-byte aligned): the replay / test entry.  Writes every element; reads nothing. */
+int bg_dropout_mask(uint8_t* mask, int M, int C, int B, double p, unsigned long long seed, unsigned draw_id, int site,
+                    long long first_sample, bg_stream_t stream);
+
 /* QKV projection with the LayerNorm fold + self-attention in ONE launch (csrc/qkv_attn.hip): sequences of an even length
  * N <= 64, all B of them equally long; key_pad (may be NULL) as bg_attn_fwd's.  x_hi [B*N, 768] raw 16-bit rows, w_qkv [2304, 768] /
  * bias / colsum as bg_gemm_ex_fwd's fold operands, stats_in [12][B*N][2] the row statistics partials of x; out [B*N, 768] = what
