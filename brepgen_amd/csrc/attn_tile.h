@@ -17,7 +17,6 @@
 #pragma once
 #include "gemm16.h"
 #include <math.h>
-#include <type_traits>
 
 namespace bg {
 
@@ -131,14 +130,6 @@ __device__ __forceinline__ void at_wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// ---- host: two run-time flags -> template arguments.  f(std::bool_constant<a>, std::bool_constant<b>) ----
-template <typename F> inline void with_bools(bool a, bool b, F&& f) {
-    if (a && b) f(std::true_type{}, std::true_type{});
-    else if (a) f(std::true_type{}, std::false_type{});
-    else if (b) f(std::false_type{}, std::true_type{});
-    else f(std::false_type{}, std::false_type{});
 }
 
 }  // namespace bg

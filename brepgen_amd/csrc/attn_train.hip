@@ -45,8 +45,7 @@ struct DropKey {
 };
 // bit e of the result: key 4 kb + e of (g, head, q) is kept
 __device__ __forceinline__ unsigned keep_nibble(const DropKey& dk, unsigned long long g, int head, int q, int kb) {
-    uint32_t c[4] = {((uint32_t)q << 16) | (uint32_t)kb, (uint32_t)g, dk.draw,
-                     AT_TAG | ((uint32_t)head << 12) | (uint32_t)((g >> 32) & 0xFFFu)};
+    uint32_t c[4] = {((uint32_t)q << 16) | (uint32_t)kb, (uint32_t)g, dk.draw, drop_word3(drop_tag_sub(AT_TAG, (uint32_t)head), g)};
     philox4x32_10(c, dk.seed_lo, dk.seed_hi);
     return (c[0] >= dk.thr ? 1u : 0u) | (c[1] >= dk.thr ? 2u : 0u) | (c[2] >= dk.thr ? 4u : 0u) | (c[3] >= dk.thr ? 8u : 0u);
 }
@@ -686,17 +685,13 @@ __global__ __launch_bounds__(256) void at_bwd32_kernel(const float* __restrict__
 
 // ---- host side ----
 static int at_drop_key(const char* who, int B, int N, double p, unsigned long long seed, unsigned draw_id, long long first_sample, DropKey& dk) {
-    BG_REQUIRE(p >= 0.0 && p < 1.0, BG_E_ARG, "%s: dropout_p = %g outside [0, 1)", who, p);      // (NaN fails too)
-    BG_REQUIRE(first_sample >= 0, BG_E_ARG, "%s: negative first_sample", who);
-    BG_REQUIRE(B < 0 || (unsigned long long)first_sample + (unsigned long long)(B > 0 ? B : 0) <= (1ull << 44), BG_E_ARG,
+    const int bad = drop_key_common(B, p, seed, draw_id, first_sample, dk.seed_lo, dk.seed_hi, dk.draw, dk.first, dk.rp);
+    BG_REQUIRE(bad != DROP_BAD_P, BG_E_ARG, "%s: dropout_p = %g outside [0, 1)", who, p);      // (NaN fails too)
+    BG_REQUIRE(bad != DROP_NEGATIVE_FIRST, BG_E_ARG, "%s: negative first_sample", who);
+    BG_REQUIRE(bad != DROP_FIRST_PAST_2_44, BG_E_ARG,
                "%s: first_sample + B = %lld + %d, the dropout counter holds global sample indices below 2^44", who, first_sample, B);
     BG_REQUIRE(p == 0.0 || N <= AT_MAX_N_DROP, BG_E_SHAPE, "%s: N = %d, the dropout counter holds sequences up to %d", who, N, AT_MAX_N_DROP);
-    dk.seed_lo = (uint32_t)seed;
-    dk.seed_hi = (uint32_t)(seed >> 32);
-    dk.draw = draw_id;
     dk.thr = (uint32_t)floor(p * 4294967296.0);
-    dk.first = (unsigned long long)first_sample;
-    dk.rp = (float)(1.0 / (1.0 - p));
     return 0;
 }
 
@@ -730,7 +725,7 @@ extern "C" int bg_attn_train_fwd(const void* qkv, const uint8_t* key_pad, void* 
                                  bg_stream_t stream) {
     AT_CHECK_COMMON("bg_attn_train_fwd");
     BG_REQUIRE(qkv && out && lse, BG_E_ARG, "bg_attn_train_fwd: null pointer (qkv, out, lse)");
-    BG_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)lse & 3) == 0, BG_E_ALIGN,
+    BG_REQUIRE(aligned(qkv, 16) && aligned(out, 16) && aligned(lse, 4), BG_E_ALIGN,
                "bg_attn_train_fwd: 16-byte alignment of qkv / out, 4-byte of lse");
     DropKey dk;
     if (const int rc = at_drop_key("bg_attn_train_fwd", B, N, dropout_p, seed, draw_id, first_sample, dk)) return rc;
@@ -781,9 +776,8 @@ extern "C" int bg_attn_bwd(const void* qkv, const uint8_t* key_pad, const float*
     BG_REQUIRE(variant != BG_ATTN_BWD_SHORT || (N <= 64 && dtype != BG_F32), BG_E_SHAPE,
                "bg_attn_bwd: the short-sequence kernel takes N <= 64 and 16-bit operands (N = %d, dtype %d)", N, dtype);
     BG_REQUIRE(qkv && lse && dout && dqkv, BG_E_ARG, "bg_attn_bwd: null pointer (qkv, lse, dout, dqkv)");
-    BG_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)dqkv & 15) == 0 &&
-                   ((uintptr_t)lse & 3) == 0 && ((uintptr_t)workspace & 3) == 0,
-               BG_E_ALIGN, "bg_attn_bwd: 16-byte alignment of qkv / dout / dqkv, 4-byte of lse / workspace");
+    BG_REQUIRE(aligned(qkv, 16) && aligned(dout, 16) && aligned(dqkv, 16) && aligned(lse, 4) && aligned(workspace, 4), BG_E_ALIGN,
+               "bg_attn_bwd: 16-byte alignment of qkv / dout / dqkv, 4-byte of lse / workspace");
     DropKey dk;
     if (const int rc = at_drop_key("bg_attn_bwd", B, N, dropout_p, seed, draw_id, first_sample, dk)) return rc;
     if (B == 0) return 0;

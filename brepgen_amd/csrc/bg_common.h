@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "../../include/brepgen_hip.h"
 
 namespace bg {
@@ -18,6 +19,16 @@ int launch_status(const char* what);   // hipGetLastError -> 0 / positive hipErr
             return (code);                     \
         }                                      \
     } while (0)
+
+// ---- host: pointer alignment to `bytes` (a power of two; null counts as aligned) ----
+inline bool aligned(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+// ---- host: two run-time flags -> template arguments.  f(std::bool_constant<a>, std::bool_constant<b>) ----
+template <typename F> inline void with_bools(bool a, bool b, F&& f) {
+    if (a && b) f(std::true_type{}, std::true_type{});
+    else if (a) f(std::true_type{}, std::false_type{});
+    else if (b) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
 
 // ---- optional per-kernel timing (bg_profile_begin / bg_profile_end; off by default, zero cost when off) ----
 enum ProfKernel { PK_GEMM_BF16_128 = 0,  /* persistent 128x128 kernel (gemm_bf16_p_kernel) */ PK_GEMM_BF16_64, PK_GEMM_F32, PK_ATTN_BF16, PK_ATTN_F32, PK_LAYERNORM,

@@ -230,12 +230,10 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(DdpmArgs a) {
     }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int ddpm_step(const DdpmArgs& a, hipStream_t s) {
     if (a.n == 0) return 0;
-    const bool vec = (a.n % 4 == 0) && aligned16(a.eps_c) && aligned16(a.eps_u) && aligned16(a.x) &&
-                     aligned16(a.noise) && aligned16(a.out);
+    const bool vec = (a.n % 4 == 0) && aligned(a.eps_c, 16) && aligned(a.eps_u, 16) && aligned(a.x, 16) &&
+                     aligned(a.noise, 16) && aligned(a.out, 16);
     ProfScope prof(PK_DDPM_STEP, 0.0, 4.0 * a.n * (3.0 + (a.eps_u ? 1 : 0) + (a.noise ? 1 : 0)), s);
     const size_t work = vec ? a.n / 4 : a.n;
     const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);

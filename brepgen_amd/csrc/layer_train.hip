@@ -224,7 +224,7 @@ __device__ __forceinline__ uint32_t lt_keep8(const LtDrop& k, uint32_t q) {
     const uint32_t r = q / k.CB, cb = q - r * k.CB;          // row, column block
     const uint32_t n = r / k.B, b = r - n * k.B;             // rows are sequence-first: token n of sample b
     const unsigned long long gs = k.first + b;
-    uint32_t c[4] = {n * k.CB + cb, (uint32_t)gs, k.draw, k.tag | (uint32_t)((gs >> 32) & 0xFFFu)};
+    uint32_t c[4] = {n * k.CB + cb, (uint32_t)gs, k.draw, drop_word3(k.tag, gs)};
     philox4x32_10(c, k.k0, k.k1);
     uint32_t m = 0;
 #pragma unroll
@@ -316,13 +316,6 @@ template <typename F> static void lt_ln_dispatch(int xd, int yd, F&& f) {
     else if (xd == BG_BF16 && yd == BG_BF16) f(LtPair<BG_BF16, BG_BF16>{});
     else f(LtPair<BG_BF16, BG_F32>{});
 }
-// (stream dtype, branch dtype): fp32 or the branch's own
-template <typename F> static void lt_drop_dispatch(int sd, int bd, F&& f) {
-    if (sd == BG_F32 && bd == BG_F16) f(LtPair<BG_F32, BG_F16>{});
-    else if (sd == BG_F32) f(LtPair<BG_F32, BG_BF16>{});
-    else if (bd == BG_F16) f(LtPair<BG_F16, BG_F16>{});
-    else f(LtPair<BG_BF16, BG_BF16>{});
-}
 
 // shape and key checks shared by the dropout entries; fills `k`.  keyed: the entry takes (B, p, seed, draw_id, site, first_sample)
 static int lt_drop_args(const char* who, int M, int C, int B, double p, unsigned long long seed, unsigned draw_id, int site,
@@ -331,15 +324,13 @@ static int lt_drop_args(const char* who, int M, int C, int B, double p, unsigned
     BG_REQUIRE(B >= 1 && M % B == 0, BG_E_SHAPE, "%s: rows are sequence-first, M = %d must be a multiple of B = %d >= 1", who, M, B);
     BG_REQUIRE((unsigned long long)M * (unsigned)(C / 8) < (1ull << 32), BG_E_SHAPE, "%s: M * C / 8 = %llu does not fit 32 bits", who,
                (unsigned long long)M * (unsigned)(C / 8));
-    BG_REQUIRE(p >= 0.0 && p < 1.0, BG_E_ARG, "%s: p = %g outside [0, 1)", who, p);
+    const int bad = drop_key_common(B, p, seed, draw_id, first_sample, k.k0, k.k1, k.draw, k.first, k.rp);
+    BG_REQUIRE(bad != DROP_BAD_P, BG_E_ARG, "%s: p = %g outside [0, 1)", who, p);
     BG_REQUIRE(site >= 0 && site <= 3, BG_E_ARG, "%s: site = %d outside 0 .. 3", who, site);
-    BG_REQUIRE(first_sample >= 0 && first_sample <= (1ll << 44) - B, BG_E_ARG, "%s: first_sample = %lld: first_sample + B must stay within 2^44", who,
-               first_sample);
-    k.k0 = (uint32_t)seed; k.k1 = (uint32_t)(seed >> 32); k.draw = draw_id; k.tag = 0xD4090000u | ((uint32_t)site << 12);
+    BG_REQUIRE(bad == DROP_OK, BG_E_ARG, "%s: first_sample = %lld: first_sample + B must stay within 2^44", who, first_sample);
+    k.tag = drop_tag_sub(0xD4090000u, (uint32_t)site);
     k.thr = (uint32_t)(p * 65536.0);                       // floor: p >= 0
     k.CB = (uint32_t)(C / 8); k.B = (uint32_t)B;
-    k.rp = (float)(1.0 / (1.0 - p));
-    k.first = (unsigned long long)first_sample;
     k.nchunks = (unsigned long long)M * (unsigned)(C / 8);
     return 0;
 }
@@ -347,7 +338,6 @@ static inline unsigned lt_chunk_grid(const LtDrop& k) {
     const unsigned long long b = (k.nchunks + 255) / 256;
     return (unsigned)(b < (unsigned long long)LT_MAX_WGS ? b : LT_MAX_WGS);
 }
-static inline bool lt_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace bg
 
@@ -360,7 +350,7 @@ extern "C" int bg_ln_train_fwd(const void* x, int x_dtype, const float* gamma, c
     BG_REQUIRE(M >= 0, BG_E_SHAPE, "bg_ln_train_fwd: M = %d is negative", M);
     BG_REQUIRE(eps >= 0.f, BG_E_ARG, "bg_ln_train_fwd: eps = %g is negative", (double)eps);
     BG_REQUIRE(M == 0 || (x && gamma && beta && y && stats), BG_E_ARG, "bg_ln_train_fwd: null pointer (x, gamma, beta, y, stats)");
-    BG_REQUIRE(lt_aligned16(x) && lt_aligned16(gamma) && lt_aligned16(beta) && lt_aligned16(y) && ((uintptr_t)stats & 7) == 0, BG_E_ALIGN,
+    BG_REQUIRE(aligned(x, 16) && aligned(gamma, 16) && aligned(beta, 16) && aligned(y, 16) && aligned(stats, 8), BG_E_ALIGN,
                "bg_ln_train_fwd: 16-byte alignment of x / gamma / beta / y, 8-byte alignment of stats");
     if (M == 0) return 0;
     const int rows8 = (M + LT_SLOTS - 1) / LT_SLOTS;
@@ -384,8 +374,8 @@ extern "C" int bg_ln_bwd(const void* dy, int y_dtype, const void* x, int x_dtype
     BG_REQUIRE(M >= 0, BG_E_SHAPE, "bg_ln_bwd: M = %d is negative", M);
     BG_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), BG_E_ARG, "bg_ln_bwd: dgamma and dbeta must be given together or both be null");
     BG_REQUIRE(M == 0 || (dy && x && stats && gamma && dx), BG_E_ARG, "bg_ln_bwd: null pointer (dy, x, stats, gamma, dx)");
-    BG_REQUIRE(lt_aligned16(dy) && lt_aligned16(x) && lt_aligned16(gamma) && lt_aligned16(dskip) && lt_aligned16(dx) && lt_aligned16(dgamma) &&
-                   lt_aligned16(dbeta) && lt_aligned16(workspace) && ((uintptr_t)stats & 7) == 0,
+    BG_REQUIRE(aligned(dy, 16) && aligned(x, 16) && aligned(gamma, 16) && aligned(dskip, 16) && aligned(dx, 16) && aligned(dgamma, 16) &&
+                   aligned(dbeta, 16) && aligned(workspace, 16) && aligned(stats, 8),
                BG_E_ALIGN, "bg_ln_bwd: 16-byte alignment of dy / x / gamma / dskip / dx / dgamma / dbeta / workspace, 8-byte alignment of stats");
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) {
@@ -421,13 +411,14 @@ extern "C" int bg_dropout_add_fwd(const void* branch, int branch_dtype, const vo
     LtDrop k;
     if (int rc = lt_drop_args("bg_dropout_add_fwd", M, C, B, p, seed, draw_id, site, first_sample, k)) return rc;
     BG_REQUIRE(M == 0 || (branch && skip && out), BG_E_ARG, "bg_dropout_add_fwd: null pointer (branch, skip, out)");
-    BG_REQUIRE(lt_aligned16(branch) && lt_aligned16(skip) && lt_aligned16(out), BG_E_ALIGN, "bg_dropout_add_fwd: 16-byte alignment of branch / skip / out");
+    BG_REQUIRE(aligned(branch, 16) && aligned(skip, 16) && aligned(out, 16), BG_E_ALIGN, "bg_dropout_add_fwd: 16-byte alignment of branch / skip / out");
     if (M == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(lt_chunk_grid(k));
-    lt_drop_dispatch(stream_dtype, branch_dtype, [&](auto pr) {
-        if (k.thr) hipLaunchKernelGGL((lt_dropout_add_kernel<decltype(pr)::a, decltype(pr)::b, true>), grid, dim3(256), 0, s, branch, skip, out, k);
-        else hipLaunchKernelGGL((lt_dropout_add_kernel<decltype(pr)::a, decltype(pr)::b, false>), grid, dim3(256), 0, s, branch, skip, out, k);
+    with_bools(branch_dtype == BG_F16, k.thr != 0, [&](auto F16, auto DROP) {      // the stream: fp32 or the branch's own dtype
+        constexpr int BD = F16() ? BG_F16 : BG_BF16;
+        if (stream_dtype == BG_F32) hipLaunchKernelGGL((lt_dropout_add_kernel<BG_F32, BD, DROP()>), grid, dim3(256), 0, s, branch, skip, out, k);
+        else hipLaunchKernelGGL((lt_dropout_add_kernel<BD, BD, DROP()>), grid, dim3(256), 0, s, branch, skip, out, k);
     });
     return launch_status("dropout_add_fwd");
 }
@@ -440,13 +431,14 @@ extern "C" int bg_dropout_bwd(const void* dout, int stream_dtype, void* dbranch,
     LtDrop k;
     if (int rc = lt_drop_args("bg_dropout_bwd", M, C, B, p, seed, draw_id, site, first_sample, k)) return rc;
     BG_REQUIRE(M == 0 || (dout && dbranch), BG_E_ARG, "bg_dropout_bwd: null pointer (dout, dbranch)");
-    BG_REQUIRE(lt_aligned16(dout) && lt_aligned16(dbranch), BG_E_ALIGN, "bg_dropout_bwd: 16-byte alignment of dout / dbranch");
+    BG_REQUIRE(aligned(dout, 16) && aligned(dbranch, 16), BG_E_ALIGN, "bg_dropout_bwd: 16-byte alignment of dout / dbranch");
     if (M == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(lt_chunk_grid(k));
-    lt_drop_dispatch(stream_dtype, branch_dtype, [&](auto pr) {
-        if (k.thr) hipLaunchKernelGGL((lt_dropout_bwd_kernel<decltype(pr)::a, decltype(pr)::b, true>), grid, dim3(256), 0, s, dout, dbranch, k);
-        else hipLaunchKernelGGL((lt_dropout_bwd_kernel<decltype(pr)::a, decltype(pr)::b, false>), grid, dim3(256), 0, s, dout, dbranch, k);
+    with_bools(branch_dtype == BG_F16, k.thr != 0, [&](auto F16, auto DROP) {
+        constexpr int BD = F16() ? BG_F16 : BG_BF16;
+        if (stream_dtype == BG_F32) hipLaunchKernelGGL((lt_dropout_bwd_kernel<BG_F32, BD, DROP()>), grid, dim3(256), 0, s, dout, dbranch, k);
+        else hipLaunchKernelGGL((lt_dropout_bwd_kernel<BD, BD, DROP()>), grid, dim3(256), 0, s, dout, dbranch, k);
     });
     return launch_status("dropout_bwd");
 }
@@ -457,17 +449,13 @@ extern "C" int bg_relu_dropout_fwd(const void* x, void* h, int dtype, int M, int
     LtDrop k;
     if (int rc = lt_drop_args("bg_relu_dropout_fwd", M, C, B, p, seed, draw_id, site, first_sample, k)) return rc;
     BG_REQUIRE(M == 0 || (x && h), BG_E_ARG, "bg_relu_dropout_fwd: null pointer (x, h)");
-    BG_REQUIRE(lt_aligned16(x) && lt_aligned16(h), BG_E_ALIGN, "bg_relu_dropout_fwd: 16-byte alignment of x / h");
+    BG_REQUIRE(aligned(x, 16) && aligned(h, 16), BG_E_ALIGN, "bg_relu_dropout_fwd: 16-byte alignment of x / h");
     if (M == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(lt_chunk_grid(k));
-    if (dtype == BG_F16) {
-        if (k.thr) hipLaunchKernelGGL((lt_relu_dropout_kernel<BG_F16, true>), grid, dim3(256), 0, s, x, h, k);
-        else hipLaunchKernelGGL((lt_relu_dropout_kernel<BG_F16, false>), grid, dim3(256), 0, s, x, h, k);
-    } else {
-        if (k.thr) hipLaunchKernelGGL((lt_relu_dropout_kernel<BG_BF16, true>), grid, dim3(256), 0, s, x, h, k);
-        else hipLaunchKernelGGL((lt_relu_dropout_kernel<BG_BF16, false>), grid, dim3(256), 0, s, x, h, k);
-    }
+    with_bools(dtype == BG_F16, k.thr != 0, [&](auto F16, auto DROP) {
+        hipLaunchKernelGGL((lt_relu_dropout_kernel<F16() ? BG_F16 : BG_BF16, DROP()>), grid, dim3(256), 0, s, x, h, k);
+    });
     return launch_status("relu_dropout_fwd");
 }
 
@@ -476,7 +464,7 @@ extern "C" int bg_relu_dropout_bwd(const void* h, const void* dh, void* dx, int 
     LtDrop k;
     if (int rc = lt_drop_args("bg_relu_dropout_bwd", M, C, 1, p, 0, 0, 0, 0, k)) return rc;
     BG_REQUIRE(M == 0 || (h && dh && dx), BG_E_ARG, "bg_relu_dropout_bwd: null pointer (h, dh, dx)");
-    BG_REQUIRE(lt_aligned16(h) && lt_aligned16(dh) && lt_aligned16(dx), BG_E_ALIGN, "bg_relu_dropout_bwd: 16-byte alignment of h / dh / dx");
+    BG_REQUIRE(aligned(h, 16) && aligned(dh, 16) && aligned(dx, 16), BG_E_ALIGN, "bg_relu_dropout_bwd: 16-byte alignment of h / dh / dx");
     if (M == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(lt_chunk_grid(k));
@@ -490,7 +478,7 @@ extern "C" int bg_dropout_mask(uint8_t* mask, int M, int C, int B, double p, uns
     LtDrop k;
     if (int rc = lt_drop_args("bg_dropout_mask", M, C, B, p, seed, draw_id, site, first_sample, k)) return rc;
     BG_REQUIRE(M == 0 || mask, BG_E_ARG, "bg_dropout_mask: null pointer (mask)");
-    BG_REQUIRE(((uintptr_t)mask & 7) == 0, BG_E_ALIGN, "bg_dropout_mask: 8-byte alignment of mask");
+    BG_REQUIRE(aligned(mask, 8), BG_E_ALIGN, "bg_dropout_mask: 8-byte alignment of mask");
     if (M == 0) return 0;
     hipLaunchKernelGGL(lt_mask_kernel, dim3(lt_chunk_grid(k)), dim3(256), 0, (hipStream_t)stream, mask, k);
     return launch_status("dropout_mask");

@@ -41,4 +41,22 @@ __device__ __forceinline__ void philox_randn4(float (&v)[4], uint32_t blk, unsig
     }
 }
 
+// ---- what the two dropout-mask families (0xAD70: attn_train.hip, 0xD409: layer_train.hip) share ----
+// word 3 of the counter = tag_sub | bits 32..43 of the GLOBAL sample index gs; tag_sub = domain tag | 4-bit sub-stream (head / site) << 12
+__host__ __device__ inline uint32_t drop_tag_sub(uint32_t tag, uint32_t sub) { return tag | (sub << 12); }
+__device__ __forceinline__ uint32_t drop_word3(uint32_t tag_sub, unsigned long long gs) { return tag_sub | (uint32_t)((gs >> 32) & 0xFFFu); }
+// host: checks p in [0, 1) (NaN fails) and 0 <= first_sample, first_sample + B <= 2^44, and fills the seed halves, draw, first and
+// rp = float(1 / (1 - p)).  Returns which check failed first, in that order; the entry words its own message (and its threshold).
+enum { DROP_OK = 0, DROP_BAD_P, DROP_NEGATIVE_FIRST, DROP_FIRST_PAST_2_44 };
+inline int drop_key_common(int B, double p, unsigned long long seed, unsigned draw_id, long long first_sample, uint32_t& seed_lo,
+                           uint32_t& seed_hi, uint32_t& draw, unsigned long long& first, float& rp) {
+    if (!(p >= 0.0 && p < 1.0)) return DROP_BAD_P;
+    if (first_sample < 0) return DROP_NEGATIVE_FIRST;
+    if ((unsigned long long)first_sample + (unsigned long long)(B > 0 ? B : 0) > (1ull << 44)) return DROP_FIRST_PAST_2_44;
+    seed_lo = (uint32_t)seed; seed_hi = (uint32_t)(seed >> 32); draw = draw_id;
+    first = (unsigned long long)first_sample;
+    rp = (float)(1.0 / (1.0 - p));
+    return DROP_OK;
+}
+
 }  // namespace bg

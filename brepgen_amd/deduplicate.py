@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
+from ._train import require_device
 from .dataset import _device
 
 P_MAX, BIT_MAX, GROUP_MAX = 1024, 16, 4096      # csrc/hash_dedup.hip
@@ -40,8 +41,7 @@ def table_size(n):
 
 def _on_device(t, what, dtype):
     _lib.load()
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise _lib.BrepgenHipError(f"{what} runs on the MI355X only (a device tensor is required); there is no CPU fallback")
+    require_device(t, what)
     if t.dtype != dtype:
         raise ValueError(f"{what}: expected {dtype}, got {t.dtype}")
     return t.contiguous()

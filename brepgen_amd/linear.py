@@ -18,23 +18,17 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._train import DTYPES, HALF, adopt, encoder_layers, fp32, require_device, workspace
 
-_DTYPES = {torch.float32: _lib.BG_F32, torch.float16: _lib.BG_F16, torch.bfloat16: _lib.BG_BF16}
-_16BIT = (torch.float16, torch.bfloat16)
 TILE = 128           # bg_linear_wgrad: N % 128 == 0 and K % 128 == 0
-
-
-def _require_device(t, what):
-    if not t.is_cuda:
-        raise _lib.BrepgenHipError(f"{what} runs on the MI355X only (a device tensor is required); there is no CPU fallback")
 
 
 def _weight_cast(lib, w, dtype, transposed):
     """16-bit copy of w [R, C] ([C, R] if transposed) in one launch"""
     R, C = w.shape
     out = torch.empty((C, R) if transposed else (R, C), dtype=dtype, device=w.device)
-    _lib.check(lib.bg_weight_cast(_lib.ptr(w), _DTYPES[w.dtype], R, C, None if transposed else _lib.ptr(out),
-                                  _lib.ptr(out) if transposed else None, _DTYPES[dtype], _lib.stream()), "bg_weight_cast")
+    _lib.check(lib.bg_weight_cast(_lib.ptr(w), DTYPES[w.dtype], R, C, None if transposed else _lib.ptr(out),
+                                  _lib.ptr(out) if transposed else None, DTYPES[dtype], _lib.stream()), "bg_weight_cast")
     return out
 
 
@@ -44,7 +38,7 @@ def _gemm(lib, a, w, bias, M, N, K):
     d = _lib.GemmDesc()
     d.a, d.lda, d.w, d.bias, d.out, d.ldc = _lib.ptr(a), K, _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), N
     d.M, d.N, d.N_pad, d.K = M, N, N, K
-    d.ab_dtype = d.out_dtype = _DTYPES[a.dtype]
+    d.ab_dtype = d.out_dtype = DTYPES[a.dtype]
     d.act, d.add_div, d.add2_div, d.ln_eps = _lib.BG_ACT_NONE, 1, 1, 1e-5
     _lib.check(lib.bg_gemm_ex_fwd(d, _lib.stream()), "bg_gemm_ex_fwd")
     return out
@@ -60,7 +54,7 @@ class _Linear(torch.autograd.Function):
         with torch.autocast(device_type="cuda", enabled=False):
             weight = weight.contiguous()
             w16 = weight if weight.dtype == x.dtype else _weight_cast(lib, weight, x.dtype, False)
-            b32 = None if bias is None else bias.detach().float().contiguous()
+            b32 = None if bias is None else fp32(bias)
             y = _gemm(lib, x2, w16.detach(), b32, M, N, K)
         ctx.save_for_backward(x2, weight)
         ctx.bias_dtype = None if bias is None else bias.dtype
@@ -86,10 +80,10 @@ class _Linear(torch.autograd.Function):
                 odt = torch.float32 if weight.dtype == torch.float32 else x2.dtype
                 dw = torch.empty(N, K, dtype=odt, device=x2.device)              # (a frozen weight with a trained bias: scratch)
                 db = torch.empty(N, dtype=odt, device=x2.device) if need_b else None
-                dt = _DTYPES[x2.dtype]
+                dt = DTYPES[x2.dtype]
                 nbytes = lib.bg_linear_wgrad_workspace_bytes(M, N, K, ctx.split)
-                ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x2.device) if nbytes else None
-                _lib.check(lib.bg_linear_wgrad(_lib.ptr(dy), N, _lib.ptr(x2), K, _lib.ptr(dw), _lib.ptr(db), M, N, K, dt, _DTYPES[odt],
+                ws = workspace(nbytes, x2.device)
+                _lib.check(lib.bg_linear_wgrad(_lib.ptr(dy), N, _lib.ptr(x2), K, _lib.ptr(dw), _lib.ptr(db), M, N, K, dt, DTYPES[odt],
                                                ctx.split, _lib.ptr(ws), nbytes, _lib.stream()), "bg_linear_wgrad")
                 if not need_w:
                     dw = None
@@ -104,7 +98,7 @@ def linear(x, weight, bias=None, split=0):
     activation-sized extra.  The backward gives dX in x's dtype and dW / db in the parameter's dtype -- fp32 parameters get the fp32
     sums unrounded.  split: bg_linear_wgrad's (0 = auto).  Works inside torch.autocast (nothing here is re-cast by it); enqueues on
     the current stream, no host synchronisation in forward or backward."""
-    if x.dtype not in _16BIT:
+    if x.dtype not in HALF:
         raise ValueError(f"linear: x of dtype {x.dtype} (fp16 or bf16: the trainers run under autocast; an fp32 product is not provided)")
     if weight.dim() != 2 or weight.dtype not in (torch.float32, x.dtype):
         raise ValueError(f"linear: weight must be [N, K] in fp32 or {x.dtype}, got {tuple(weight.shape)} {weight.dtype}")
@@ -117,16 +111,16 @@ def linear(x, weight, bias=None, split=0):
         raise ValueError(f"linear: bias must be [{N}] in fp32 or {x.dtype}, got {tuple(bias.shape)} {bias.dtype}")
     if not 0 <= int(split) <= 64:
         raise ValueError(f"linear: split = {split} outside [0, 64]")
-    _require_device(x, "linear")
-    _require_device(weight, "linear (weight)")
+    require_device(x, "linear")
+    require_device(weight, "linear (weight)")
     if bias is not None:
-        _require_device(bias, "linear (bias)")
+        require_device(bias, "linear (bias)")
     return _Linear.apply(x, weight, bias, int(split))
 
 
 def linear_autocast(x, weight, bias, what="DeviceLinear"):
     """`linear` after casting a non-16-bit x to the autocast dtype, as autocast would for F.linear; outside autocast such an x raises"""
-    if x.dtype not in _16BIT:
+    if x.dtype not in HALF:
         if not torch.is_autocast_enabled("cuda"):
             raise ValueError(f"{what}: input of dtype {x.dtype} outside torch.autocast (fp16 / bf16 input, or run under autocast)")
         x = x.to(torch.get_autocast_dtype("cuda"))
@@ -146,10 +140,7 @@ class DeviceLinear(nn.Linear):
 
 
 def _shared(old):
-    new = DeviceLinear(old.in_features, old.out_features, bias=old.bias is not None, device="meta")
-    new.weight, new.bias = old.weight, old.bias
-    new.train(old.training)
-    return new
+    return adopt(DeviceLinear(old.in_features, old.out_features, bias=old.bias is not None, device="meta"), old, "weight", "bias")
 
 
 def use_device_linear(encoder):
@@ -160,9 +151,7 @@ def use_device_linear(encoder):
     parameters itself).  The embed MLPs and fc_out of the denoisers are not touched: their shapes are no multiples of 128.  Returns the
     encoder."""
     from .attention import MultiheadSelfAttention
-    if not hasattr(encoder, "layers"):
-        raise ValueError("use_device_linear: an nn.TransformerEncoder (an object with .layers) is required")
-    for layer in encoder.layers:
+    for layer in encoder_layers(encoder, "use_device_linear"):
         for holder, name in ((layer, "linear1"), (layer, "linear2"), (layer.self_attn, "out_proj")):
             old = getattr(holder, name)
             if isinstance(old, DeviceLinear):

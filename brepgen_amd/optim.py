@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from ._lib import check, stream
+from ._train import require_device
 
 CHUNK, MAX_BLOCKS = 4096, 2048                     # BG_OPTIM_CHUNK, BG_OPTIM_MAX_BLOCKS of include/brepgen_hip.h
 
@@ -53,11 +54,6 @@ def _check_param(p, what="parameter"):
         raise ValueError(f"{what}: expected torch.float32, got {p.dtype} (16-bit parameters and moments are not provided)")
     if not p.is_contiguous():
         raise ValueError(f"{what} of shape {tuple(p.shape)} is not contiguous")
-
-
-def _require_device(t, what):
-    if not t.is_cuda:
-        raise _lib.BrepgenHipError(f"{what} runs on the MI355X only (a device tensor is required); there is no CPU fallback")
 
 
 def _chunks_of(numels):
@@ -177,7 +173,7 @@ class AdamW:
         c = self._slots.get(id(p))
         if c is not None and st is c[0] and st.get("exp_avg") is c[1] and st.get("exp_avg_sq") is c[2]:
             return c[3]
-        _require_device(p, "AdamW.step")
+        require_device(p, "AdamW.step")
         if st is None:
             st = self.state[p] = {}
         for k in ("exp_avg", "exp_avg_sq"):
@@ -350,7 +346,7 @@ class GradScaler:
     def scale(self, loss):
         """loss * scale as a device multiplication (the scale is read on the device)."""
         _lib.load()
-        _require_device(loss, "GradScaler.scale")
+        require_device(loss, "GradScaler.scale")
         return loss * self._device_state(loss.device)[:4].view(torch.float32)[0]
 
     @torch.no_grad()
@@ -428,7 +424,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
     rows = np.zeros(len(grads), _ROW)
     for i, g in enumerate(grads):
         _check_param(g, "gradient")
-        _require_device(g, "clip_grad_norm_")
+        require_device(g, "clip_grad_norm_")
         if g.device != grads[0].device:
             raise ValueError("gradients on more than one device")
         rows[i]["g"], rows[i]["numel"] = g.data_ptr(), g.numel()

@@ -5,18 +5,10 @@ import numpy as np
 import torch
 
 from brepgen_amd import _lib
+from tests.hip_ops import DT, _p, _stream
 
 H, DH, D = 12, 64, 768
-DT = {torch.float32: _lib.BG_F32, torch.float16: _lib.BG_F16, torch.bfloat16: _lib.BG_BF16}
 MASK_KINDS = ("none", "tail", "scattered", "one_empty")
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def train_fwd(qkv, key_pad, B, N, scale=0.125, p=0.0, seed=0, draw=0, first=0, out=None, lse=None):

@@ -8,12 +8,13 @@ import torch
 from brepgen_amd import _lib
 from brepgen_amd._lib import BG_ACT_NONE, BG_ACT_RELU, BG_BF16, BG_F16, BG_F32, check, ptr, stream  # noqa: F401
 
-_DT = {torch.float32: BG_F32, torch.bfloat16: BG_BF16, torch.float16: BG_F16}
+DT = {torch.float32: BG_F32, torch.bfloat16: BG_BF16, torch.float16: BG_F16}
+NAME = {torch.float16: "fp16", torch.bfloat16: "bf16", torch.float32: "fp32"}
 
 
 def bg_dtype(dt):
     try:
-        return _DT[dt]
+        return DT[dt]
     except KeyError:
         raise TypeError(f"brepgen_amd supports float32, bfloat16 and float16 compute, not {dt}") from None
 
@@ -44,6 +45,10 @@ def layernorm(x, gamma, beta, out_dtype=torch.float32, eps=1e-5, silu=False, out
     check(_lib.load().bg_layernorm_fwd(ptr(x), ptr(gamma.contiguous()), ptr(beta.contiguous()), ptr(y),
                                        bg_dtype(out_dtype), M, eps, int(silu), stream()), "bg_layernorm_fwd")
     return y
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _p(t):

@@ -4,22 +4,13 @@ TEST INFRASTRUCTURE."""
 import torch
 
 from brepgen_amd import _lib
+from tests.hip_ops import DT, NAME, _p, _stream  # noqa: F401
 
 C_LN = 768
-DT = {torch.float32: _lib.BG_F32, torch.float16: _lib.BG_F16, torch.bfloat16: _lib.BG_BF16}
-NAME = {torch.float16: "fp16", torch.bfloat16: "bf16", torch.float32: "fp32"}
 LN_PAIRS = ((torch.float32, torch.float32), (torch.float32, torch.float16), (torch.float32, torch.bfloat16),
             (torch.float16, torch.float16), (torch.bfloat16, torch.bfloat16))                                  # (x, y)
 U24 = 2.0 ** -24
 MAX_WGS, SLOTS = 2048, 8
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def chain_rows(M):

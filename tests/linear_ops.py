@@ -3,19 +3,11 @@ helpers), plus the slicing rule restated in Python.  TEST INFRASTRUCTURE."""
 import torch
 
 from brepgen_amd import _lib
+from tests.hip_ops import DT, NAME, _p, _stream  # noqa: F401
 
-DT = {torch.float32: _lib.BG_F32, torch.float16: _lib.BG_F16, torch.bfloat16: _lib.BG_BF16}
 ROW_STEP = 32                       # rows of M a workgroup stages per step (include/brepgen_hip.h: bg_linear_wgrad)
 LAYERS = {"in_proj": (2304, 768), "out_proj": (768, 768), "linear1": (1024, 768), "linear2": (768, 1024)}      # (N, K)
 U24 = 2.0 ** -24
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def auto_split(M, N, K):

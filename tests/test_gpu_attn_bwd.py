@@ -17,7 +17,6 @@ same bounds.  lse: 1e-3 for the 16-bit kernels (above); the fp32 kernel accumula
 BG_ATTN_PARITY_JSON=<path> makes the run write the measured pairs there (profiles/r13/attn_bwd_parity.json is such a run)."""
 import copy
 import json
-import os
 
 import numpy as np
 import pytest
@@ -32,6 +31,7 @@ from tests import attn_bwd_restate as R
 from tests import attn_train_ops as ops
 from tests import hip_ops
 from tests.guarded import guarded
+from tests.train_check import Parity, encoder, encoder_grads, errs, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -204,10 +204,6 @@ def test_bitwise_invariants(dtype, N, variant):
     assert not torch.equal(o4.view(torch.uint8), out[2:].view(torch.uint8))
 
 
-def _same_bytes(a, b):
-    return torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
 @pytest.mark.parametrize("p", [0.0, 0.1])
 @pytest.mark.parametrize("N", [5, 33, 64])
 @pytest.mark.parametrize("dtype", HALF, ids=["fp16", "bf16"])
@@ -218,7 +214,7 @@ def test_short_and_general_backward_agree_on_dq_bit_for_bit(dtype, N, p):
     case = ops.make_case(3, N, "one_empty", 7000 + N, dtype)
     short = _kernel(case, dtype, p, 99, 4, variant=SHORT)[2]
     general = _kernel(case, dtype, p, 99, 4, variant=GENERAL)[2]
-    assert _same_bytes(short[..., :768], general[..., :768])
+    assert same_bits(short[..., :768], general[..., :768], typed=False)
 
 
 @pytest.mark.parametrize("N", [5, 33, 64])
@@ -231,7 +227,7 @@ def test_training_forward_equals_the_inference_kernel_bit_for_bit(dtype, N):
     qkv = case["qkv_t"].cuda().reshape(B * N, 2304)
     kp = _dev(case["key_pad"].astype(np.uint8))
     out_train, _ = ops.train_fwd(qkv, kp, B, N, 1.0, 0.0)
-    assert _same_bytes(out_train, hip_ops.attention(qkv, kp, B, N))
+    assert same_bits(out_train, hip_ops.attention(qkv, kp, B, N), typed=False)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "fp16", "bf16"])
@@ -272,11 +268,6 @@ def test_guarded_buffers(dtype, N):
     assert torch.isfinite(go.view.float()).all() and torch.isfinite(gd.view.float()).all() and torch.isfinite(gl.view).all()
 
 
-def _err(a, ref):
-    d = (a.double() - ref).abs()
-    return float(d.max()), float(d.mean())
-
-
 def test_autograd_under_autocast_with_a_scaled_loss():
     """MultiheadSelfAttention against nn.MultiheadAttention with the same weights under fp16 autocast and a GradScaler-scaled loss: the
     weight gradients' error against fp64 is within twice torch's own."""
@@ -309,7 +300,7 @@ def test_autograd_under_autocast_with_a_scaled_loss():
         grads[name] = {k: getattr(mod, k).grad / 65536.0 for k in ("in_proj_weight",)}
         grads[name]["out_proj.weight"] = mod.out_proj.weight.grad / 65536.0
     for k, ref in (("in_proj_weight", ref64.in_proj_weight.grad), ("out_proj.weight", ref64.out_proj.weight.grad)):
-        (mm, ma), (tm, ta) = _err(grads["mine"][k], ref), _err(grads["torch"][k], ref)
+        (mm, ma), (tm, ta) = errs(grads["mine"][k], ref), errs(grads["torch"][k], ref)
         print("autocast", k, mm, ma, tm, ta)
         assert torch.isfinite(grads["mine"][k]).all() and mm <= 2 * tm and ma <= 2 * ta, (k, mm, ma, tm, ta)
 
@@ -326,42 +317,28 @@ def test_an_inf_in_dout_reaches_the_gradients_of_its_sample_only(dtype):
     assert not torch.isfinite(g[1]).all() and torch.isfinite(g[0]).all() and torch.isfinite(g[2]).all()
 
 
-def _encoder(dropout):
-    torch.manual_seed(11)
-    enc = nn.TransformerEncoder(nn.TransformerEncoderLayer(768, 12, 1024, dropout=dropout, norm_first=True), 2, nn.LayerNorm(768),
-                                enable_nested_tensor=False)
-    return enc.cuda()
-
-
-def _run(enc, x, kpm, w):
-    enc.zero_grad()
-    y = enc(x, src_key_padding_mask=kpm)
-    (y * w).sum().backward()
-    return y.detach(), {k: p.grad.clone() for k, p in enc.named_parameters()}
-
-
 def test_two_layer_encoder_forward_and_backward_fp32():
-    enc = _encoder(0.0)
+    enc = encoder(0.0, 11)
     torch.manual_seed(12)
     x, w = torch.randn(7, 3, 768, device="cuda"), torch.randn(7, 3, 768, device="cuda") / 64
     kpm = torch.zeros(3, 7, dtype=torch.bool, device="cuda")
     kpm[0, 5:] = True
     kpm[2, 2:] = True
-    _, g64 = _run(copy.deepcopy(enc).double(), x.double(), kpm, w.double())
-    y_t, g_t = _run(enc, x, kpm, w)
+    _, g64 = encoder_grads(copy.deepcopy(enc).double(), x.double(), kpm, w.double(), fp64=False)
+    y_t, g_t = encoder_grads(enc, x, kpm, w, fp64=False)
     keys = list(enc.state_dict())
     bga.use_device_attention(enc)
     assert list(enc.state_dict()) == keys
-    y_m, g_m = _run(enc, x, kpm, w)
+    y_m, g_m = encoder_grads(enc, x, kpm, w, fp64=False)
     assert float((y_m - y_t).abs().max()) <= 1e-4
     L = 2
     for k in g64:
-        (mm, ma), (tm, ta) = _err(g_m[k], g64[k]), _err(g_t[k], g64[k])
+        (mm, ma), (tm, ta) = errs(g_m[k], g64[k]), errs(g_t[k], g64[k])
         assert mm <= 2 * L * tm + 1e-30 and ma <= 2 * L * ta + 1e-30, (k, mm, ma, tm, ta)
 
 
 def test_two_layer_encoder_dropout_streams():
-    enc = bga.use_device_attention(_encoder(0.1), seed=77)
+    enc = bga.use_device_attention(encoder(0.1, 11), seed=77)
     torch.manual_seed(13)
     x, w = torch.randn(7, 3, 768, device="cuda"), torch.randn(7, 3, 768, device="cuda") / 64
     kpm = torch.zeros(3, 7, dtype=torch.bool, device="cuda")
@@ -372,7 +349,7 @@ def test_two_layer_encoder_dropout_streams():
         torch.manual_seed(99)                                  # the layers' own nn.Dropout draws from torch's generator
         for m in mods:
             m.calls = calls
-        return _run(enc, x, kpm, w)
+        return encoder_grads(enc, x, kpm, w, fp64=False)
 
     enc.train()
     y0, g0 = run(0)
@@ -383,18 +360,18 @@ def test_two_layer_encoder_dropout_streams():
     assert [m.calls for m in mods] == [1, 1]
     # eval(): no mask anywhere -- the bits of an encoder built with dropout = 0
     enc.eval()
-    y_e, g_e = _run(enc, x, kpm, w)
-    plain = bga.use_device_attention(_encoder(0.0))
+    y_e, g_e = encoder_grads(enc, x, kpm, w, fp64=False)
+    plain = bga.use_device_attention(encoder(0.0, 11))
     plain.load_state_dict(enc.state_dict())
     plain.train()
-    y_p, g_p = _run(plain, x, kpm, w)
+    y_p, g_p = encoder_grads(plain, x, kpm, w, fp64=False)
     assert torch.equal(y_e, y_p) and all(torch.equal(g_e[k], g_p[k]) for k in g_e)
 
 
 def test_eval_and_no_grad_forward_of_the_converted_encoder():
     """eval() / no_grad of the surrounding torch layers still works after the swap (the fast-path check reads the module's attributes)
     and gives the stock encoder's result."""
-    enc = _encoder(0.1).eval()
+    enc = encoder(0.1, 11).eval()
     torch.manual_seed(14)
     x = torch.randn(7, 3, 768, device="cuda")
     kpm = torch.zeros(3, 7, dtype=torch.bool, device="cuda")
@@ -410,10 +387,6 @@ def test_eval_and_no_grad_forward_of_the_converted_encoder():
 
 def test_zz_write_parity_pairs():
     """Not a check of its own: writes the pairs measured above where BG_ATTN_PARITY_JSON points."""
-    path = os.environ.get("BG_ATTN_PARITY_JSON")
-    if path and _PAIRS:
-        with open(path, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "torch": torch.__version__,
-                       "note": "absolute error against fp64, pooled over B in {1, 3} x four masks per (dtype, N); torch = autograd of "
-                               "F.scaled_dot_product_attention (math backend) for p0, of the explicit-mask formula for dropout",
-                       "pairs": _PAIRS}, f, indent=1)
+    if _PAIRS:
+        Parity("BG_ATTN_PARITY_JSON", "absolute error against fp64, pooled over B in {1, 3} x four masks per (dtype, N); torch = autograd of "
+               "F.scaled_dot_product_attention (math backend) for p0, of the explicit-mask formula for dropout").write(_PAIRS)

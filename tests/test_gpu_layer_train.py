@@ -15,13 +15,10 @@ inputs.
 BG_LAYER_PARITY_JSON=<path> makes the run write the measured pairs there (profiles/r15/layer_train_parity.json is such a run)."""
 import copy
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 import brepgen_amd as bga
@@ -30,55 +27,19 @@ from tests import attn_train_ops as aops
 from tests import layer_ops as ops
 from tests import layer_restate as R
 from tests.guarded import guarded, strided_input
+from tests.train_check import Parity, bits, encoder, encoder_grads, errs, pooled, same_bits
 
 pytestmark = pytest.mark.gpu
 NAME = ops.NAME
 MS = (1, 3, 4, 5, 63, 64, 65, 129, 257, 1000)
 EPS = float(np.float32(1e-5))          # what the kernels and torch's fp32 LayerNorm both use
-PAIRS = []
 PAIR_IDS = [f"{NAME[a]}-{NAME[b]}" for a, b in ops.LN_PAIRS]
 FIRSTS = (0, 2 ** 33 + 3)
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _parity_json():
-    yield
-    path = os.environ.get("BG_LAYER_PARITY_JSON")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
-        with open(path, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "torch": torch.__version__,
-                       "note": "absolute error against fp64 from the same rounded inputs; LayerNorm pairs are pooled over M in "
-                               f"{list(MS)}; torch = torch.native_layer_norm in fp32 and its autograd, or stock autocast for the encoder",
-                       "pairs": PAIRS}, f, indent=1)
-
-
-def errs(got, ref):
-    e = (got.double() - ref).abs()
-    return float(e.max()), float(e.mean())
-
-
-def pooled(parts):
-    e = torch.cat([p.reshape(-1) for p in parts])
-    return float(e.max()), float(e.mean())
-
-
-def record(case, what, ours, torchs):
-    PAIRS.append({"case": case, "what": what, "max": ours[0], "mean": ours[1], "torch_max": torchs[0], "torch_mean": torchs[1]})
-    print(f"{case} {what}: max {ours[0]:.3e} (torch {torchs[0]:.3e})  mean {ours[1]:.3e} (torch {torchs[1]:.3e})")
-
-
-def within_2x(case, what, ours, torchs):
-    record(case, what, ours, torchs)
-    assert ours[0] <= 2 * torchs[0] and ours[1] <= 2 * torchs[1], (case, what, ours, torchs)
-
-
-def bits(t):
-    return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
+PARITY = Parity("BG_LAYER_PARITY_JSON", "absolute error against fp64 from the same rounded inputs; LayerNorm pairs are pooled over M in "
+                f"{list(MS)}; torch = torch.native_layer_norm in fp32 and its autograd, or stock autocast for the encoder")
+record, within_2x, _parity_json = PARITY.record, PARITY.within_2x, PARITY.fixture()
 
 
 @functools.lru_cache(maxsize=None)
@@ -417,17 +378,6 @@ def test_elementwise_guarded(M, stream):
 
 # ---- in the encoder ----
 
-def _encoder(dropout, seed):
-    torch.manual_seed(seed)
-    enc = nn.TransformerEncoder(nn.TransformerEncoderLayer(768, 12, 1024, dropout=dropout, norm_first=True), 2, norm=nn.LayerNorm(768),
-                                enable_nested_tensor=False).cuda().train()
-    with torch.no_grad():
-        for m in enc.modules():
-            if isinstance(m, nn.LayerNorm):
-                m.weight.add_(0.1 * torch.randn_like(m.weight)), m.bias.add_(0.1 * torch.randn_like(m.bias))
-    return enc
-
-
 def _inputs(N, B):
     x = torch.randn(N, B, 768, device="cuda")
     g = torch.randn(N, B, 768, device="cuda", dtype=torch.float64) / (N * B)
@@ -437,31 +387,20 @@ def _inputs(N, B):
     return x, g * (~mask).t().unsqueeze(-1), mask                           # padded tokens carry no loss, as in the trainers
 
 
-def _encoder_grads(enc, x, mask, g, scale, dtype):
-    enc.zero_grad(set_to_none=True)
-    if dtype is None:
-        out = enc(x.double(), src_key_padding_mask=mask)
-    else:
-        with torch.autocast("cuda", dtype=dtype):
-            out = enc(x, src_key_padding_mask=mask)
-    ((out.double() * g).sum() * scale).backward()
-    return out.detach(), {k: p.grad.double() / scale for k, p in enc.named_parameters()}
-
-
 @pytest.mark.parametrize("stream", ("fp32_stream", "fp16_stream"))
 @pytest.mark.parametrize("N", (5, 33))
 def test_layer_in_the_encoder_without_dropout(N, stream):
     B, scale = 3, 2.0 ** 10
-    base = _encoder(0.0, N)
+    base = encoder(0.0, N, jitter_norms=True)
     x, g, mask = _inputs(N, B)
     if stream == "fp16_stream":
         x = x.half()
-    _, ref = _encoder_grads(copy.deepcopy(base).double(), x, mask, g, 1.0, None)
-    _, plain = _encoder_grads(copy.deepcopy(base), x, mask, g, scale, torch.float16)
+    _, ref = encoder_grads(copy.deepcopy(base).double(), x, mask, g, 1.0, None)
+    _, plain = encoder_grads(copy.deepcopy(base), x, mask, g, scale, torch.float16)
     enc = copy.deepcopy(base)
     assert L.use_device_layer(enc) is enc
     assert all(isinstance(l, L.DeviceEncoderLayer) for l in enc.layers) and isinstance(enc.norm, L.DeviceLayerNorm)
-    out, ours = _encoder_grads(enc, x, mask, g, scale, torch.float16)
+    out, ours = encoder_grads(enc, x, mask, g, scale, torch.float16)
     assert list(ours) == list(ref) and out.dtype == torch.float32
     for k in ref:
         assert enc.get_parameter(k).grad.dtype == torch.float32
@@ -518,12 +457,12 @@ def _reset_calls(enc, calls):
 @pytest.mark.parametrize("N", (5, 33))
 def test_layer_in_the_encoder_with_dropout(N):
     B, scale, p, seed = 3, 2.0 ** 10, 0.1, 77
-    base0 = _encoder(0.0, N)
-    base = _encoder(p, N)
+    base0 = encoder(0.0, N, jitter_norms=True)
+    base = encoder(p, N, jitter_norms=True)
     base.load_state_dict(base0.state_dict())
     x, g, mask = _inputs(N, B)
     enc = L.use_device_layer(copy.deepcopy(base), seed=seed)
-    out, ours = _encoder_grads(enc, x, mask, g, scale, torch.float16)
+    out, ours = encoder_grads(enc, x, mask, g, scale, torch.float16)
     assert all(l.calls == 1 and l.self_attn.calls == 1 for l in enc.layers)
     # the masks of that step: layer i drew draw_id = 0 * 2 + i, in its attention module and in its three dropouts
     masks = []
@@ -540,10 +479,10 @@ def test_layer_in_the_encoder_with_dropout(N):
         within_2x(f"encoder N={N} dropout {p}", k, errs(ours[k], ref[k]), errs(plain[k], ref[k]))
     # resetting the call counters replays the step bit for bit; another counter value draws other masks
     _reset_calls(enc, 0)
-    out2, again = _encoder_grads(enc, x, mask, g, scale, torch.float16)
+    out2, again = encoder_grads(enc, x, mask, g, scale, torch.float16)
     assert same_bits(out2, out) and all(torch.equal(again[k], ours[k]) for k in ours)
     _reset_calls(enc, 5)
-    out3, _ = _encoder_grads(enc, x, mask, g, scale, torch.float16)
+    out3, _ = encoder_grads(enc, x, mask, g, scale, torch.float16)
     assert not same_bits(out3, out)
     # eval(): no mask -- the bits of an encoder built with dropout = 0
     enc0 = L.use_device_layer(copy.deepcopy(base0))

@@ -10,7 +10,6 @@ inputs, with two kinds of bound:
 BG_LINEAR_PARITY_JSON=<path> makes the run write the measured pairs there (profiles/r14/linear_bwd_parity.json is such a run)."""
 import copy
 import functools
-import json
 import os
 
 import pytest
@@ -22,36 +21,13 @@ import brepgen_amd as bga
 from brepgen_amd import linear as L
 from tests import linear_ops as ops
 from tests.guarded import guarded, strided_input
+from tests.train_check import Parity, encoder_grads, errs
 
 pytestmark = pytest.mark.gpu
 DTYPES = (torch.float16, torch.bfloat16)
-NAME = {torch.float16: "fp16", torch.bfloat16: "bf16", torch.float32: "fp32"}
-PAIRS = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _parity_json():
-    yield
-    path = os.environ.get("BG_LINEAR_PARITY_JSON")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
-        with open(path, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "pairs": PAIRS}, f, indent=1)
-
-
-def errs(got, ref):
-    e = (got.double() - ref).abs()
-    return float(e.max()), float(e.mean())
-
-
-def record(case, what, ours, torchs):
-    PAIRS.append({"case": case, "what": what, "max": ours[0], "mean": ours[1], "torch_max": torchs[0], "torch_mean": torchs[1]})
-    print(f"{case} {what}: max {ours[0]:.3e} (torch {torchs[0]:.3e})  mean {ours[1]:.3e} (torch {torchs[1]:.3e})")
-
-
-def within_2x(case, what, ours, torchs):
-    record(case, what, ours, torchs)
-    assert ours[0] <= 2 * torchs[0] and ours[1] <= 2 * torchs[1], (case, what, ours, torchs)
+NAME = ops.NAME
+PARITY = Parity("BG_LINEAR_PARITY_JSON")
+record, within_2x, _parity_json = PARITY.record, PARITY.within_2x, PARITY.fixture()
 
 
 @functools.lru_cache(maxsize=None)
@@ -273,17 +249,6 @@ def test_linear_autograd_against_fp64(shape, N, dtype):
 
 # ---- in the encoder layer ----
 
-def _layer_grads(enc, x, mask, g, scale, dtype):
-    enc.zero_grad(set_to_none=True)
-    if dtype is None:
-        out = enc(x.double(), src_key_padding_mask=mask)
-    else:
-        with torch.autocast("cuda", dtype=dtype):
-            out = enc(x, src_key_padding_mask=mask)
-    ((out.double() * g).sum() * scale).backward()
-    return {k: p.grad.double() / scale for k, p in enc.named_parameters()}
-
-
 @pytest.mark.parametrize("with_attention", (False, True), ids=("torch_attention", "device_attention"))
 @pytest.mark.parametrize("N", (5, 33))
 def test_linear_in_the_encoder_layer(N, with_attention):
@@ -296,13 +261,13 @@ def test_linear_in_the_encoder_layer(N, with_attention):
     for b in range(B):
         mask[b, max(1, (N * (b + 2)) // (B + 2)):] = True                    # ragged: another length per sample
     g = g * (~mask).t().unsqueeze(-1)                                       # padded tokens carry no loss, as in the trainers
-    ref = _layer_grads(copy.deepcopy(base).double(), x, mask, g, 1.0, None)
-    plain = _layer_grads(copy.deepcopy(base), x, mask, g, scale, torch.float16)
+    ref = encoder_grads(copy.deepcopy(base).double(), x, mask, g, 1.0, None)[1]
+    plain = encoder_grads(copy.deepcopy(base), x, mask, g, scale, torch.float16)[1]
     enc = copy.deepcopy(base)
     if with_attention:
         bga.use_device_attention(enc)
     assert L.use_device_linear(enc) is enc
-    ours = _layer_grads(enc, x, mask, g, scale, torch.float16)
+    ours = encoder_grads(enc, x, mask, g, scale, torch.float16)[1]
     assert list(ours) == list(ref)
     for k in ref:
         assert enc.get_parameter(k).grad.dtype == torch.float32

@@ -274,6 +274,35 @@ def test_use_device_layer_refuses_what_it_does_not_run():
     assert isinstance(enc.layers[0], nn.TransformerEncoderLayer)              # nothing was converted before the refusal
 
 
+def test_dropout_draw_state_of_the_attention_module_and_the_layer():
+    """_train.DropoutDraws, the one draw state of MultiheadSelfAttention and DeviceEncoderLayer: draw_id = (calls * n_layers +
+    layer_index) mod 2^32, a forward that drops nothing leaves it alone, seed / calls replay it, every instance counts for itself."""
+    from brepgen_amd import _train
+    enc = L.use_device_layer(_stock(layers=3), seed=5)
+    layer, attn = enc.layers[1], enc.layers[1].self_attn
+    assert isinstance(layer, _train.DropoutDraws) and isinstance(attn, _train.DropoutDraws)
+    for m in (layer, attn):
+        assert (m.seed, m.calls, m.layer_index, m.n_layers, m.first_sample) == (5, 0, 1, 3, 0)
+    fresh = bga.MultiheadSelfAttention()
+    assert (fresh.seed, fresh.calls, fresh.layer_index, fresh.n_layers, fresh.first_sample) == (None, 0, 0, 1, 0)
+    assert layer.draw_key(False) == (5, 0) and fresh.draw_key(False) == (0, 0) and (layer.calls, fresh.calls, fresh.seed) == (0, 0, None)
+    assert [layer.draw_key(True) for _ in range(3)] == [(5, 1), (5, 4), (5, 7)] and layer.calls == 3
+    assert attn.calls == 0 and enc.layers[0].calls == 0 and attn.draw_key(True) == (5, 1) and layer.calls == 3      # counters of their own
+    layer.seed, layer.calls = 9, 1                                             # replay from the second forward, under another seed
+    assert [layer.draw_key(True) for _ in range(2)] == [(9, 4), (9, 7)]
+    # the wrap: calls just below 2^32 / n_layers
+    layer.calls = 2 ** 32 // 3 - 1                                             # 3 * (calls + 1) + 1 == 2^32
+    assert [layer.next_draw_id() for _ in range(3)] == [2 ** 32 - 3, 0, 3] and layer.calls == 2 ** 32 // 3 + 2
+    # the default seed is fixed at the first forward that drops, from the CPU generator's state
+    torch.manual_seed(1234)
+    from brepgen_amd.sampling import noise_key
+    assert fresh.draw_key(True) == (noise_key(), 0) and fresh.seed == noise_key() and fresh.draw_key(True) == (fresh.seed, 1)
+    # the three converters refuse an object without .layers alike
+    for convert in (bga.use_device_attention, bga.use_device_linear, L.use_device_layer):
+        with pytest.raises(ValueError, match=r"an object with \.layers"):
+            convert(nn.Linear(768, 768))
+
+
 def test_layer_train_kernels_use_no_scratch_and_do_not_spill():
     """the check tests/test_abi_cpu.py::test_hand_scheduled_kernels_do_not_spill makes for its files"""
     from brepgen_amd import build as b

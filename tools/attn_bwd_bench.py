@@ -26,8 +26,9 @@ every call (forward, backward) between its own pair of device events; reported i
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from bench_common import med, phases, run_children
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,10 +36,6 @@ sys.path.insert(0, ROOT)
 SHAPES = [(512, 30), (512, 50), (512, 64), (64, 1500)]
 MFMA_PEAK = 2.5e15
 H, DH, D = 12, 64, 768
-
-
-def med(v):
-    return sorted(v)[len(v) // 2]
 
 
 def child(B, N, iters, rounds, warmup):
@@ -89,30 +86,19 @@ def child(B, N, iters, rounds, warmup):
                 fns["hip_general"] = ours_general
             grad_of = {name: (dout_s if name == "torch_split" else dout) for name in fns}
 
-            def clear():
-                qkv.grad = qs.grad = ks_.grad = vs.grad = None
+            def fwd_bwd(name, f):
+                def call():
+                    qkv.grad = qs.grad = ks_.grad = vs.grad = None
+                    a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                    a.record()
+                    o = f()
+                    b.record()
+                    o.backward(grad_of[name])
+                    c.record()
+                    return a, b, c
+                return call
 
-            for name, f in fns.items():
-                for _ in range(warmup):
-                    clear()
-                    f().backward(grad_of[name])
-            torch.cuda.synchronize()
-            ms = {k: {"fwd": [], "bwd": []} for k in fns}
-            for _ in range(rounds):
-                for name, f in fns.items():
-                    ev = []
-                    for _ in range(iters):
-                        clear()
-                        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-                        a.record()
-                        o = f()
-                        b.record()
-                        o.backward(grad_of[name])
-                        c.record()
-                        ev.append((a, b, c))
-                    torch.cuda.synchronize()
-                    ms[name]["fwd"].append(sum(a.elapsed_time(b) for a, b, _ in ev) / iters)
-                    ms[name]["bwd"].append(sum(b.elapsed_time(c) for _, b, c in ev) / iters)
+            ms = phases(torch, {name: fwd_bwd(name, f) for name, f in fns.items()}, iters, rounds, warmup, 2, all_rounds=True)
             gemm = 2.0 * B * H * N * N * DH
             es = 2
             row_bytes = B * N * D * es
@@ -121,9 +107,9 @@ def child(B, N, iters, rounds, warmup):
             row = {"B": B, "N": N, "dtype": str(dtype)[6:], "dropout_p": p, "torch_backend": backend,
                    "mask_fill": round(float((~kpm).float().mean()), 3)}
             for name in fns:
-                fw, bw = med(ms[name]["fwd"]), med(ms[name]["bwd"])
+                fw, bw = med(ms[name][0]), med(ms[name][1])
                 row[name] = {"fwd_ms": round(fw, 4), "bwd_ms": round(bw, 4), "total_ms": round(fw + bw, 4),
-                             "bwd_rounds_ms": [round(x, 4) for x in ms[name]["bwd"]]}
+                             "bwd_rounds_ms": [round(x, 4) for x in ms[name][1]]}
             bw = row["hip"]["bwd_ms"] * 1e-3
             n_exec = 8 if N <= 64 else 12              # short kernel: S, dP once, dQ / dK / dV twice each (hi + lo); general: see above
             row["hip"].update({"bwd_products_executed": n_exec, "bwd_tflops_executed": round(n_exec * gemm / bw / 1e12, 2),
@@ -152,25 +138,8 @@ def main():
     if args.child:
         print("ROWS " + json.dumps(child(args.child[0], args.child[1], args.iters, args.rounds, args.warmup)))
         return 0
-    rows, failed = [], None
-    for B, N in SHAPES:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", str(B), str(N),
-               "--iters", str(args.iters), "--rounds", str(args.rounds), "--warmup", str(args.warmup)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        got = [ln for ln in r.stdout.splitlines() if ln.startswith("ROWS ")]
-        if r.returncode != 0 or not got:
-            failed = {"B": B, "N": N, "returncode": r.returncode, "stderr": r.stderr[-2000:]}
-            print(json.dumps(failed), file=sys.stderr)
-            break                                           # nothing more is started on the device after a failure
-        rows += json.loads(got[0][5:])
-        for row in json.loads(got[0][5:]):
-            print(json.dumps(row), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump({"mfma_peak_flops": MFMA_PEAK, "iters_per_round": args.iters, "rounds": args.rounds, "rows": rows, "failed": failed}, f,
-                  indent=1)
-    print(json.dumps({"out": args.out, "rows": len(rows), "failed": failed is not None}))
-    return 1 if failed else 0
+    return run_children(__file__, SHAPES, ("B", "N"), ("--iters", args.iters, "--rounds", args.rounds, "--warmup", args.warmup), args.timeout,
+                        args.out, {"mfma_peak_flops": MFMA_PEAK, "iters_per_round": args.iters, "rounds": args.rounds})
 
 
 if __name__ == "__main__":

@@ -20,6 +20,8 @@ import time
 import numpy as np
 import torch
 
+from bench_common import med
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -40,10 +42,6 @@ def event_ms(fn):
     b.record()
     b.synchronize()
     return a.elapsed_time(b), res
-
-
-def med(v):
-    return sorted(v)[len(v) // 2]
 
 
 def real2bit(data, n_bits):                 # convert_utils.real2bit as it stands in the reference

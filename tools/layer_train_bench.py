@@ -20,8 +20,9 @@ another and stops at the first that fails).  In a child:
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from bench_common import phases, run_children, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -29,45 +30,6 @@ sys.path.insert(0, ROOT)
 SHAPES = [(512, 30), (512, 60), (64, 1500)]          # (B, N)
 STREAM_RATE = 6.3e12
 P, SEED = 0.1, 77
-
-
-def med(v):
-    return sorted(v)[len(v) // 2]
-
-
-def windows(torch, fns, launches, rounds, warmup):
-    """{name: median ms per launch}: fns[name]() enqueues one launch"""
-    for f in fns.values():
-        for _ in range(warmup):
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(rounds):
-        for name, f in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(launches):
-                f()
-            b.record()
-            torch.cuda.synchronize()
-            ms[name].append(a.elapsed_time(b) / launches)
-    return {k: med(v) for k, v in ms.items()}
-
-
-def phases(torch, fns, iters, rounds, warmup, n=2):
-    """{name: [median ms per phase]}: fns[name]() runs one call and returns the n + 1 events it recorded"""
-    for f in fns.values():
-        for _ in range(warmup):
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [[] for _ in range(n)] for k in fns}
-    for _ in range(rounds):
-        for name, f in fns.items():
-            evs = [f() for _ in range(iters)]
-            torch.cuda.synchronize()
-            for p in range(n):
-                ms[name][p].append(sum(e[p].elapsed_time(e[p + 1]) for e in evs) / iters)
-    return {k: [med(v) for v in per] for k, per in ms.items()}
 
 
 def kernel_rows(torch, B, N, sdt, launches, rounds, warmup):
@@ -154,7 +116,7 @@ def op_rows(torch, B, N, sdt, iters, rounds, warmup):
     }
     rows = []
     for name, (ours, theirs, leaves, grads) in cases.items():
-        t = phases(torch, {"hip": run(ours, leaves, grads), "torch": run(theirs, leaves, grads)}, iters, rounds, warmup)
+        t = phases(torch, {"hip": run(ours, leaves, grads), "torch": run(theirs, leaves, grads)}, iters, rounds, warmup, 2)
         row = {"op": name}
         for k in ("hip", "torch"):
             row[k] = {"fwd_ms": round(t[k][0], 4), "bwd_ms": round(t[k][1], 4), "total_ms": round(sum(t[k]), 4)}
@@ -194,7 +156,7 @@ def encoder_row(torch, B, N, iters, rounds, warmup):
             return a, c, d
         return call
 
-    t = phases(torch, {k: run(e) for k, e in encs.items()}, iters, rounds, warmup)
+    t = phases(torch, {k: run(e) for k, e in encs.items()}, iters, rounds, warmup, 2)
     row = {k: {"fwd_ms": round(v[0], 3), "bwd_ms": round(v[1], 3), "total_ms": round(sum(v), 3)} for k, v in t.items()}
     row["spread_parent_vs_itself"] = round(abs(row["parent"]["total_ms"] - row["parent_again"]["total_ms"]) / row["parent"]["total_ms"], 4)
     row["layer_over_parent"] = round(row["layer"]["total_ms"] / row["parent"]["total_ms"], 4)
@@ -221,26 +183,11 @@ def main():
     ap.add_argument("--child", type=int, nargs=2, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        print("ROW " + json.dumps(child(args.child[0], args.child[1], args)))
+        print("ROWS " + json.dumps([child(args.child[0], args.child[1], args)]))
         return 0
-    rows, failed = [], None
-    for B, N in SHAPES:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", str(B), str(N),
-               "--launches", str(args.launches), "--rounds", str(args.rounds), "--warmup", str(args.warmup)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        got = [ln for ln in r.stdout.splitlines() if ln.startswith("ROW ")]
-        if r.returncode != 0 or not got:
-            failed = {"B": B, "N": N, "returncode": r.returncode, "stderr": r.stderr[-2000:]}
-            print(json.dumps(failed), file=sys.stderr)
-            break                                           # nothing more is started on the device after a failure
-        rows.append(json.loads(got[0][4:]))
-        print(got[0][4:], flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump({"stream_rate_bytes_per_s": STREAM_RATE, "launches_per_window": args.launches, "rounds": args.rounds, "dropout_p": P,
-                   "rows": rows, "failed": failed}, f, indent=1)
-    print(json.dumps({"out": args.out, "rows": len(rows), "failed": failed is not None}))
-    return 1 if failed else 0
+    return run_children(__file__, SHAPES, ("B", "N"), ("--launches", args.launches, "--rounds", args.rounds, "--warmup", args.warmup),
+                        args.timeout, args.out, {"stream_rate_bytes_per_s": STREAM_RATE, "launches_per_window": args.launches,
+                                                 "rounds": args.rounds, "dropout_p": P})
 
 
 if __name__ == "__main__":

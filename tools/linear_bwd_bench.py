@@ -22,8 +22,9 @@ between its own pair of device events on one stream; reported is the median roun
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from bench_common import device_state, phases, run_children
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -34,40 +35,10 @@ SPLITS = (1, 2, 4, 8, 16, 32)
 MFMA_PEAK, HBM_RATE = 2.5e15, 8e12
 
 
-def med(v):
-    return sorted(v)[len(v) // 2]
-
-
 def no_empty_slice(M, S, row_step=32):
     """bg_linear_wgrad's slicing rule (include/brepgen_hip.h): a forced split that leaves a slice empty is rejected"""
     steps = (M + row_step - 1) // row_step
     return (S - 1) * ((steps + S - 1) // S) * row_step < M
-
-
-def device_state(torch):
-    out = {}
-    for key, fn in (("clock_mhz", "clock_rate"), ("power_draw", "power_draw"), ("temperature_c", "temperature")):
-        try:
-            out[key] = int(getattr(torch.cuda, fn)())
-        except Exception as e:                                                                      # noqa: BLE001
-            out[key] = f"not available ({type(e).__name__})"
-    return out
-
-
-def timed(torch, fns, iters, rounds, warmup, phases=1):
-    """{name: [median ms per phase]}; fns[name]() runs one call and returns the events it recorded (phases + 1 of them)"""
-    for f in fns.values():
-        for _ in range(warmup):
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [[] for _ in range(phases)] for k in fns}
-    for _ in range(rounds):
-        for name, f in fns.items():
-            evs = [f() for _ in range(iters)]
-            torch.cuda.synchronize()
-            for p in range(phases):
-                ms[name][p].append(sum(e[p].elapsed_time(e[p + 1]) for e in evs) / iters)
-    return {k: [med(v) for v in per] for k, per in ms.items()}
 
 
 def child(M, iters, rounds, warmup):
@@ -106,7 +77,7 @@ def child(M, iters, rounds, warmup):
                 return call
 
             splits = [S for S in SPLITS if no_empty_slice(M, S)]
-            t_w = timed(torch, {str(S): wgrad(S) for S in splits}, iters, rounds, warmup)
+            t_w = phases(torch, {str(S): wgrad(S) for S in splits}, iters, rounds, warmup)
 
             def fwd_bwd(fn):
                 def call():
@@ -121,11 +92,11 @@ def child(M, iters, rounds, warmup):
                     return a, c, d
                 return call
 
-            t_op = timed(torch, {"hip": fwd_bwd(L.linear), "torch": fwd_bwd(F.linear)}, iters, rounds, warmup, phases=2)
+            t_op = phases(torch, {"hip": fwd_bwd(L.linear), "torch": fwd_bwd(F.linear)}, iters, rounds, warmup, 2)
             state = device_state(torch)
             flop = 2.0 * M * N * K
             need = 2.0 * M * (N + K) + 4.0 * N * (K + 1)
-            t_walk = timed(torch, {"xcd": wgrad(auto), "plain": wgrad(auto, 1)}, iters, rounds, warmup)
+            t_walk = phases(torch, {"xcd": wgrad(auto), "plain": wgrad(auto, 1)}, iters, rounds, warmup)
             os.environ.pop("BG_LINEAR_WGRAD_WALK", None)
             t_auto = t_walk["xcd"][0]
             best = min(splits, key=lambda S: t_w[str(S)][0])
@@ -157,25 +128,9 @@ def main():
     if args.child:
         print("ROWS " + json.dumps(child(args.child, args.iters, args.rounds, args.warmup)))
         return 0
-    rows, failed = [], None
-    for M in TOKENS:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", str(M),
-               "--iters", str(args.iters), "--rounds", str(args.rounds), "--warmup", str(args.warmup)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        got = [ln for ln in r.stdout.splitlines() if ln.startswith("ROWS ")]
-        if r.returncode != 0 or not got:
-            failed = {"M": M, "returncode": r.returncode, "stderr": r.stderr[-2000:]}
-            print(json.dumps(failed), file=sys.stderr)
-            break                                           # nothing more is started on the device after a failure
-        rows += json.loads(got[0][5:])
-        for row in json.loads(got[0][5:]):
-            print(json.dumps(row), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump({"mfma_peak_flops": MFMA_PEAK, "hbm_stream_rate": HBM_RATE, "iters_per_round": args.iters, "rounds": args.rounds,
-                   "rows": rows, "failed": failed}, f, indent=1)
-    print(json.dumps({"out": args.out, "rows": len(rows), "failed": failed is not None}))
-    return 1 if failed else 0
+    return run_children(__file__, [(M,) for M in TOKENS], ("M",), ("--iters", args.iters, "--rounds", args.rounds, "--warmup", args.warmup),
+                        args.timeout, args.out, {"mfma_peak_flops": MFMA_PEAK, "hbm_stream_rate": HBM_RATE, "iters_per_round": args.iters,
+                                                 "rounds": args.rounds})
 
 
 if __name__ == "__main__":

@@ -26,15 +26,13 @@ import warnings
 
 import torch
 
+from bench_common import med
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE_BYTES_PER_S = 6.3e12
 BYTES_PER_PARAM = 32
-
-
-def med(v):
-    return sorted(v)[len(v) // 2]
 
 
 def make_variant(kind, shapes, hyper, max_norm, seed):
