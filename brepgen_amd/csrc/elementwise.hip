@@ -190,7 +190,12 @@ struct DdpmArgs {
 
 __device__ __forceinline__ float ddpm_one(float e, float x, float z, const DdpmArgs& a, bool has_noise) {
     float x0 = (x - a.sqrt_beta_prod * e) / a.sqrt_alpha_prod;
-    if (a.clip > 0.f) x0 = fminf(fmaxf(x0, -a.clip), a.clip);
+    if (a.clip > 0.f) {
+        // torch.clamp, which upstream clips with: +-inf goes to the bound, NaN stays NaN (fminf / fmaxf would return the bound
+        // for a NaN, and an overflowed eps evaluation would come out as a finite sample).  Both comparisons are false for NaN.
+        x0 = x0 < -a.clip ? -a.clip : x0;
+        x0 = x0 > a.clip ? a.clip : x0;
+    }
     float o = a.x0_coeff * x0 + a.xt_coeff * x;
     if (has_noise) o += a.sigma * z;
     return o;

@@ -7,11 +7,13 @@ trainer.py:285-292; ``set_timesteps`` / ``timesteps`` / ``step(...).prev_sample`
 Host side: the per-step scalar coefficients are computed in float32 numpy in upstream's operation order.
 Device side: ``bg_cfg_ddpm_step`` / ``bg_pndm_step`` read eps (optionally the two halves of a classifier-free
 guidance batch, combined in-kernel), the sample, the noise / PLMS history, and write prev_sample -- one pass.
+A timestep is taken by value whether it lives on the host or on a device (``_TimestepByValue``).
 
 Extensions over upstream (all keyword-only, default = upstream behaviour):
   noise=...      inject the ancestral noise (upstream draws it from the global device RNG, sample.py:153)
   guidance=(w)   with model_output of batch 2B: eps = eps[:B]*(1+w) - eps[B:]*w fused into the step
 """
+import weakref
 from types import SimpleNamespace
 
 import numpy as np
@@ -57,7 +59,65 @@ def _prep(t):
     return t.detach().to(torch.float32).contiguous()
 
 
-class DDPMScheduler:
+def _version(t):
+    """A tensor's version counter, or None for a tensor made under torch.inference_mode(), which keeps none: such a tensor cannot be
+    known unchanged, so it is read every time."""
+    try:
+        return t._version
+    except RuntimeError:
+        return None
+
+
+class _TimestepByValue:
+    """The timestep a step uses equals ``int(timestep)``, always.  What differs is how a DEVICE timestep gets to the host: a
+    caller that follows the reference literally iterates device timesteps and passes 0-d device tensors, and `int()` of one
+    stalls the host on everything enqueued so far, at every step.
+
+      1. a host timestep (Python / numpy int, one-element CPU tensor) is used as given;
+      2. a one-element view of the scheduler's own `self.timesteps` on a device (`set_timesteps(n, device=...)`, then
+         slicing / iteration / unbind / reshape(-1) / strided slices) is never read: the view's storage offset is its position
+         in the schedule, which `set_timesteps` built on the host -- as long as nobody has written to that tensor since;
+      3. any other device tensor is READ.  A view (`for t in timesteps.cuda()[-250:]`) costs one copy of its base per base
+         tensor and version, then every view of it is indexed by storage offset; a tensor without a base costs one `int()`.
+
+    Nothing is ever guessed from the order of the calls.  `_timestep_reads` counts the device-to-host reads."""
+
+    def _seat_timesteps(self, ts, device=None):
+        self._host_ts = [int(v) for v in ts]
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._ts_version = _version(self.timesteps)
+        self._ts_memo = None                    # (weakref to a base tensor, its _version, its elements on the host)
+        if not hasattr(self, "_timestep_reads"):
+            self._timestep_reads = 0
+
+    def _timestep(self, timestep):
+        if not torch.is_tensor(timestep) or timestep.device.type == "cpu":
+            return int(timestep)
+        if timestep.numel() != 1:
+            raise ValueError("scheduler.step takes one timestep")
+        own = self.timesteps
+        if own.device.type != "cpu" and self._ts_version is not None and _version(own) == self._ts_version and (
+                timestep._base is own or timestep is own) and timestep.dtype == own.dtype:
+            return self._host_ts[timestep.storage_offset() - own.storage_offset()]
+        return self._read_timestep(timestep)
+
+    def _read_timestep(self, timestep):
+        base = timestep._base
+        # the memo is keyed on the base OBJECT (weakly) and its version, never on data_ptr(): the caching allocator hands the
+        # same address to the next tensor
+        version = _version(base) if base is not None else None
+        if version is None or base.dtype != timestep.dtype or base.storage_offset() != 0 or not base.is_contiguous():
+            t = int(timestep)
+            self._timestep_reads += 1
+            return t
+        memo = self._ts_memo
+        if memo is None or memo[0]() is not base or memo[1] != version:
+            memo = self._ts_memo = (weakref.ref(base), version, base.detach().reshape(-1).cpu().tolist())
+            self._timestep_reads += 1
+        return int(memo[2][timestep.storage_offset()])
+
+
+class DDPMScheduler(_TimestepByValue):
     order = 1
     init_noise_sigma = 1.0
 
@@ -74,30 +134,7 @@ class DDPMScheduler:
         self.betas, self.alphas_cumprod = _alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule)
         self._acp = self.alphas_cumprod.numpy().astype(np.float32)
         self.num_inference_steps = None
-        self._set_schedule(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64), None)
-
-    def _set_schedule(self, ts, device):
-        self._host_ts, self._cursor = [int(v) for v in ts], 0
-        self.timesteps = torch.from_numpy(ts).to(device)
-
-    def _timestep(self, timestep):
-        """The step's timestep as a host integer WITHOUT a device synchronisation.  A caller that follows the reference
-        literally iterates `scheduler.timesteps.cuda()` and passes 0-d device tensors: `int()` of one would stall the host on
-        everything enqueued so far, at every step.  The schedule is host state (set_timesteps built it), so a device timestep is
-        taken from it by position -- the steps of a schedule are consumed in order, as sample.py:126-202 does, and the cursor
-        wraps for the next sampling run; a host timestep (int / CPU tensor) is used as given and re-seats the cursor."""
-        if torch.is_tensor(timestep) and timestep.device.type != "cpu":
-            t = self._host_ts[self._cursor % len(self._host_ts)]
-            self._cursor += 1
-            return t
-        t = int(timestep)
-        n = len(self._host_ts)
-        c = self._cursor % n
-        if self._host_ts[c] == t:
-            self._cursor = c + 1
-        elif t in self._host_ts:
-            self._cursor = self._host_ts.index(t) + 1
-        return t
+        self._seat_timesteps(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -110,7 +147,7 @@ class DDPMScheduler:
         ratio = T // num_inference_steps
         ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
         ts += self.config.steps_offset
-        self._set_schedule(ts, device)
+        self._seat_timesteps(ts, device)
 
     def _coefficients(self, t):
         T = self.config.num_train_timesteps
@@ -167,7 +204,7 @@ class DDPMScheduler:
         return self.config.num_train_timesteps
 
 
-class PNDMScheduler:
+class PNDMScheduler(_TimestepByValue):
     order = 1
     init_noise_sigma = 1.0
 
@@ -186,8 +223,7 @@ class PNDMScheduler:
         self.pndm_order = 4
         self.num_inference_steps = None
         self._reset()
-        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
-        self._host_ts = [int(v) for v in self.timesteps]
+        self._seat_timesteps(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
         self.prk_timesteps = np.array([], dtype=np.int64)
 
     def _reset(self):
@@ -209,8 +245,7 @@ class PNDMScheduler:
         self.prk_timesteps = (prk[:-1].repeat(2)[1:-1])[::-1].copy()
         self.plms_timesteps = _t[:-3][::-1].copy()
         ts = np.concatenate([self.prk_timesteps, self.plms_timesteps]).astype(np.int64)
-        self.timesteps = torch.from_numpy(ts).to(device)
-        self._host_ts = [int(v) for v in ts]
+        self._seat_timesteps(ts, device)
         self._reset()
 
     def _prev_coeffs(self, t, prev_t):
@@ -224,12 +259,7 @@ class PNDMScheduler:
     def step(self, model_output, timestep, sample, return_dict=True, *, guidance=None):
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps first")
-        if torch.is_tensor(timestep) and timestep.device.type != "cpu":
-            # no device synchronisation (see DDPMScheduler._timestep): PNDM is stateful anyway -- evaluation number `counter` of the
-            # schedule IS timesteps[counter], as upstream's own step_prk / step_plms assume
-            t = self._host_ts[self.counter % len(self._host_ts)]
-        else:
-            t = int(timestep)
+        t = self._timestep(timestep)        # by value; `counter` selects the phase only, as upstream's does
         x = _prep(sample)
         eps_c, eps_u, w = _split_guidance(_prep(model_output), x, guidance)
         ratio = self.config.num_train_timesteps // self.num_inference_steps

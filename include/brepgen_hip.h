@@ -457,7 +457,7 @@ int bg_encoder_layer_fwd(const bg_layer_weights* L, int dtype, float* x, const u
 
 /* DDPMScheduler.step fused with the classifier-free-guidance combine (sample.py:132-134):
  *   eps = eps_c*(1+w) - eps_u*w   (eps_u NULL -> eps = eps_c)
- *   x0  = clamp((x - sqrt_beta_prod*eps) / sqrt_alpha_prod, +-clip)   (clip <= 0: no clamp)
+ *   x0  = clamp((x - sqrt_beta_prod*eps) / sqrt_alpha_prod, +-clip)   (clip <= 0: no clamp; as torch.clamp: NaN stays NaN)
  *   out = x0_coeff*x0 + xt_coeff*x + sigma*noise                      (noise NULL or sigma==0: skipped)
  * scalars are computed on the host in fp32 (brepgen_amd.schedulers).  n = element count. */
 int bg_cfg_ddpm_step(const float* eps_c, const float* eps_u, float guidance_w, const float* x,

@@ -343,21 +343,28 @@ def test_ctypes_structs_match_the_header(tmp_path):
 
 def test_scheduler_step_takes_a_device_timestep_without_reading_it():
     """sample.py iterates `scheduler.timesteps` -- on the device if the caller moved them there -- and hands each 0-d tensor to
-    step(): `int()` of a device tensor is a synchronisation per step.  The schedule is host state, so the product takes a device
-    timestep from it by position.  A `meta` tensor stands in for the device tensor here: reading it would raise."""
+    step(): `int()` of a device tensor is a synchronisation per step.  The schedule is host state, so a view of the scheduler's own
+    device schedule is resolved from its storage offset, by VALUE and without a read; any other device tensor is read, never guessed
+    (tests/test_schedulers_cpu.py has the full list).  A `meta` tensor stands in for the device tensor here: reading it raises."""
+    import pytest
     import torch
     from brepgen_amd.schedulers import DDPMScheduler, PNDMScheduler
     d = DDPMScheduler(num_train_timesteps=1000)
-    d.set_timesteps(1000)
-    dev_t = torch.empty((), dtype=torch.int64, device="meta")
-    assert [d._timestep(dev_t) for _ in range(3)] == [999, 998, 997]
-    assert d._timestep(torch.tensor(500)) == 500 and d._timestep(dev_t) == 499      # a host timestep re-seats the cursor
-    assert d._timestep(7) == 7 and d._timestep(dev_t) == 6
-    d.set_timesteps(50)
-    assert [d._timestep(dev_t) for _ in range(2)] == [980, 960]
-    for _ in range(48):
-        d._timestep(dev_t)
-    assert d._timestep(dev_t) == 980                                                 # wraps for the next sampling run
+    d.set_timesteps(1000, device="meta")
+    ts = d.timesteps
+    assert [d._timestep(t) for t in ts[-250:]][:3] == [249, 248, 247]
+    assert [d._timestep(t) for t in ts[::100]] == [999, 899, 799, 699, 599, 499, 399, 299, 199, 99]
+    assert [d._timestep(ts[i]) for i in (5, 900, 0)] == [994, 99, 999]
+    assert d._timestep(ts[750:751]) == 249
+    stale = ts[0]
+    d.set_timesteps(50, device="meta")
+    assert [d._timestep(t) for t in d.timesteps][:2] == [980, 960]
+    with pytest.raises((RuntimeError, NotImplementedError)):
+        d._timestep(stale)                                                           # a view from before set_timesteps: read
+    with pytest.raises((RuntimeError, NotImplementedError)):
+        d._timestep(torch.empty((), dtype=torch.int64, device="meta"))               # a bare device scalar: read
+    assert d._timestep(torch.tensor(500)) == 500 and d._timestep(7) == 7             # host timesteps are used as given
+    assert d._timestep_reads == 0
     p = PNDMScheduler(num_train_timesteps=1000)
     p.set_timesteps(200)
     assert p._host_ts[:5] == [int(v) for v in p.timesteps[:5]] and len(p._host_ts) == 209
