@@ -14,6 +14,7 @@ Drop-in for the reference's call surface on that path only:
     nn.MultiheadAttention in net.train() (attention core, dropout, backward) (attention.py) -> bg_attn_train_fwd / bg_attn_bwd
     nn.Linear of the encoder layers under autocast (forward, dX, dW + db) (linear.py) -> bg_weight_cast / bg_gemm_ex_fwd / bg_linear_wgrad
     nn.LayerNorm, ReLU, nn.Dropout and the residual adds of the encoder layers in net.train() (layer.py) -> bg_ln_train_fwd / bg_ln_bwd / bg_dropout_add_fwd / bg_relu_dropout_fwd
+    the denoisers' embed MLPs / time_embed / fc_out and the masked-MSE loss in training (mlp.py, training.mse_loss) -> bg_thin_expand / bg_thin_contract / bg_thin_wgrad / bg_ln_silu_train_fwd / bg_ln_silu_bwd / bg_masked_mse_bwd
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from . import optim  # noqa: F401
@@ -53,6 +54,10 @@ __all__ += list(_LINEAR)
 # the rest of an encoder layer in training: LayerNorm forward / backward, dropout + residual add, ReLU + dropout (layer.py)
 _LAYER = ("layer_norm", "dropout_add", "relu_dropout", "DeviceLayerNorm", "DeviceEncoderLayer", "use_device_layer")
 __all__ += list(_LAYER)
+# the denoisers' MLPs in training (mlp.py) and the differentiable loss / the one-call conversion of a denoiser (training.py)
+_MLP = ("thin_linear_in", "thin_linear_out", "ln_silu", "DeviceMLP", "use_device_mlps")
+_TRAINING = ("mse_loss", "use_device_training")
+__all__ += list(_MLP + _TRAINING)
 
 
 def __getattr__(name):
@@ -80,4 +85,10 @@ def __getattr__(name):
     if name in _LAYER:
         from . import layer
         return getattr(layer, name)
+    if name in _MLP:
+        from . import mlp
+        return getattr(mlp, name)
+    if name in _TRAINING:
+        from . import training
+        return getattr(training, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

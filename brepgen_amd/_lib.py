@@ -206,6 +206,14 @@ _SIGNATURES = {
                                       C.c_longlong, vp]),
     "bg_relu_dropout_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp]),
     "bg_dropout_mask": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_uint, C.c_int, C.c_longlong, vp]),
+    "bg_thin_expand": (C.c_int, [vp, C.c_int, C.c_int, fp, C.c_int, fp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "bg_thin_contract": (C.c_int, [vp, C.c_int, fp, fp, fp, C.c_int, C.c_int, vp]),
+    "bg_thin_wgrad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "bg_thin_wgrad": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]),
+    "bg_ln_silu_train_fwd": (C.c_int, [vp, C.c_int, fp, fp, vp, C.c_int, fp, C.c_int, C.c_float, vp]),
+    "bg_ln_silu_bwd_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "bg_ln_silu_bwd": (C.c_int, [vp, C.c_int, vp, C.c_int, fp, fp, fp, vp, fp, fp, C.c_int, vp, C.c_size_t, vp]),
+    "bg_masked_mse_bwd": (C.c_int, [fp, fp, u8p, C.c_longlong, C.c_int, C.c_int, C.c_int, fp, fp, fp, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -11,7 +11,7 @@ The trainers run under torch.autocast with fp32 master parameters: x arrives (or
 weight is cast per call by one launch, y and dX come out in x's dtype, and dW / db are written in fp32 straight from the fp32
 accumulators (torch's autocast rounds dW to 16 bits and casts it back).  An fp32 product is not provided.  LayerNorm, ReLU and
 dropout are layer.py's (layer.use_device_layer); the embed MLPs of the denoisers (first Linear K = 6 / 12 / 48, output Linear
-N = 3 .. 18: no multiple of 128) stay torch.
+N = 3 .. 48: no multiple of 128) are mlp.py's thin products (mlp.use_device_mlps).
 """
 import torch
 import torch.nn as nn

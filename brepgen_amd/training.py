@@ -1,8 +1,8 @@
 """Forward half of the reference's LDM trainers on the device: VAE encode -> latent tokens
 -> ``add_noise`` -> eps-net -> masked MSE, i.e. everything ``trainer.py`` does between loading a batch and calling
-``backward()``, and all of its ``test_val`` loops (trainer.py:374-408, 557-602, 752-797, 975-1030).  There is no backward
-pass here -- the package implements the denoising (inference) path; this module lets the same kernels compute the
-training / validation *losses* of a checkpoint.  ``vae_loss`` / ``vae_validation`` are the same for the two VAE trainers
+``backward()``, and all of its ``test_val`` loops (trainer.py:374-408, 557-602, 752-797, 975-1030).  These functions run under
+``no_grad`` on the package's inference modules: they let the same kernels compute the training / validation *losses* of a
+checkpoint (the differentiable loss is ``mse_loss``, below).  ``vae_loss`` / ``vae_validation`` are the same for the two VAE trainers
 (SurfVAETrainer / EdgeVAETrainer, trainer.py:62-129, 190-259): encode -> sample the posterior -> decode -> MSE + 1e-6 KL.
 
 Every function takes and returns device tensors and enqueues on the current stream; nothing synchronises.
@@ -38,6 +38,77 @@ def masked_mse(pred, target, mask=None, cols=None):
     check(_lib.load().bg_masked_mse(ptr(p), ptr(t), ptr(mk), rows, C, c0, c1 - c0, ptr(scratch), ptr(out), stream()),
           "bg_masked_mse")
     return {"mean": out[0], "row_mean_sum": out[1], "rows": out[2]}
+
+
+def _row_mask(mask, pred):
+    """mask broadcast over pred's rows (EdgePosNet: the [B, S] face mask over [B, S, E, 6] edges), as uint8, or None"""
+    if mask is None:
+        return None
+    if mask.dim() < pred.dim() - 1:
+        mask = mask.unsqueeze(-1).expand(pred.shape[:-1])
+    if mask.shape != pred.shape[:-1]:
+        raise ValueError(f"mse_loss: mask {tuple(mask.shape)} does not cover the rows of pred {tuple(pred.shape)}")
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
+
+
+class _MseLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, mask, cols):
+        lib = _lib.load()
+        C = pred.shape[-1]
+        p, t = pred.contiguous(), target.contiguous()
+        rows = p.numel() // C
+        scratch = torch.empty(1024, device=p.device, dtype=torch.float64)
+        out = torch.empty(3, device=p.device, dtype=torch.float32)
+        check(lib.bg_masked_mse(ptr(p), ptr(t), ptr(mask), rows, C, cols[0], cols[1] - cols[0], ptr(scratch), ptr(out), stream()), "bg_masked_mse")
+        ctx.save_for_backward(p, t, mask, out)
+        ctx.dims = (rows, C, cols)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        p, t, mask, out = ctx.saved_tensors
+        rows, C, cols = ctx.dims
+        g = g.detach().to(torch.float32).contiguous()
+        dpred = torch.empty_like(p)
+        check(_lib.load().bg_masked_mse_bwd(ptr(p), ptr(t), ptr(mask), rows, C, cols[0], cols[1] - cols[0], ptr(out), ptr(g), ptr(dpred), stream()),
+              "bg_masked_mse_bwd")
+        return dpred, None, None, None
+
+
+def mse_loss(pred, target, mask=None, cols=None):
+    """``nn.MSELoss()(pred[~mask], target[~mask])`` as a differentiable scalar (trainer.py:354, 537, 732, 950): forward ``bg_masked_mse``,
+    backward ``bg_masked_mse_bwd`` -- dpred = 2 (pred - target) g / (valid rows * columns) on the compared elements and exactly 0
+    elsewhere, the count of valid rows read on the device, so neither direction synchronises (``pred[~mask]`` does).
+
+    pred [..., C] fp32, or fp16 / bf16 as autocast's fc_out hands it over (cast to fp32 first, as autocast's mse_loss does); target
+    fp32 [..., C], must not require a gradient; mask bool [...] (True = padded), broadcast over trailing row dimensions as in
+    ``ldm_loss``; cols (start, stop) or None.  With no valid row the loss and its gradient are 0."""
+    if target.requires_grad:
+        raise ValueError("mse_loss: target requires a gradient; only pred is differentiated")
+    if pred.shape != target.shape or pred.dim() < 1 or not pred.is_floating_point():
+        raise ValueError(f"mse_loss: pred {tuple(pred.shape)} {pred.dtype} and target {tuple(target.shape)} must be floating tensors of one shape")
+    C = pred.shape[-1]
+    c0, c1 = (0, C) if cols is None else (int(cols[0]), int(cols[1]))
+    if not 0 <= c0 < c1 <= C:
+        raise ValueError(f"mse_loss: cols = {cols} outside the {C} columns")
+    if not pred.is_cuda or not target.is_cuda:
+        raise _lib.BrepgenHipError(f"mse_loss runs on the MI355X only (tensors on {pred.device} / {target.device}); no CPU fallback")
+    with torch.autocast(device_type="cuda", enabled=False):
+        return _MseLoss.apply(pred.float(), target.detach().float(), _row_mask(mask, pred), (c0, c1))
+
+
+def use_device_training(model, seed=None):
+    """Convert a reference-keyed denoiser (``net``: the nn.TransformerEncoder; the embed MLPs, ``time_embed`` and ``fc_out`` as direct
+    children) for training on this library: ``layer.use_device_layer(model.net, seed)`` and ``mlp.use_device_mlps(model)``.
+    Parameter objects and state_dict keys are unchanged.  Launches nothing.  Returns the model."""
+    from .layer import use_device_layer
+    from .mlp import use_device_mlps
+    if not hasattr(model, "net"):
+        raise ValueError("use_device_training: a denoiser with its nn.TransformerEncoder as .net is required")
+    use_device_layer(model.net, seed)
+    return use_device_mlps(model)
 
 
 def augment(ddpm, conditions, generator=None, max_t=15):

@@ -276,6 +276,57 @@ int bg_relu_dropout_bwd(const void* h, const void* dh, void* dx, int dtype, int 
 int bg_dropout_mask(uint8_t* mask, int M, int C, int B, double p, unsigned long long seed, unsigned draw_id, int site,
                     long long first_sample, bg_stream_t stream);
 
+/* ---- the denoisers' MLPs and loss in TRAINING (csrc/mlp_train.hip): nn.Sequential(Linear(k, 768), LayerNorm, SiLU, Linear(768, n))
+ * with a THIN side -- the data embeds' k = 6 / 12 / 48 and fc_out's n = 6 / 18 / 48 (network.py:1076-1099) -- and the gradient of
+ * the masked MSE.  The thin dimension s (n) is 1 .. 48, BG_E_SHAPE otherwise; the wide one is 768.  The [M, 768] operands are dense
+ * and 16-byte aligned; the thin operands are read element by element, so they need element alignment only and may be strided.  Nothing
+ * is allocated, no atomics, one writer per output element, every sum in the order stated: two calls give the same bits.  M == 0 returns
+ * 0 without a launch (bg_thin_wgrad: zeros).  fma(a, b, c) below is the fused multiply-add, one rounding. */
+
+/* y [M, 768] (y_dtype: any of the three) = x [M, s] W + b.  x: x_dtype (any of the three), row stride ldx >= s in elements -- a column
+ * slice of wider rows is read in place, its other columns never.  W fp32: w_k_major == 0 takes it as [768, s] (an embed's first
+ * nn.Linear weight), w_k_major != 0 as [s, 768] (fc_out's last weight, for its data gradient dA = dY W).  b fp32 [768] or NULL (= 0).
+ * Order: acc = b[c]; acc = fma(x[m, k], W(k, c), acc) for k = 0 .. s - 1; rounded once to y_dtype. */
+int bg_thin_expand(const void* x, int x_dtype, int ldx, const float* w, int w_k_major, const float* b, void* y, int y_dtype, int M,
+                   int s, bg_stream_t stream);
+/* y fp32 [M, n] dense = a [M, 768] W^T + b: fc_out's last Linear.  a 16-bit (a_dtype), W fp32 [n, 768] read as it is (no 16-bit
+ * copy: the product keeps fp32 weights), b fp32 [n] or NULL.  Order: a half-wave owns a row, lane l the columns 8 (l + 32 j) + e;
+ * p = 0; p = fma(a[m, c], W[i, c], p) over j = 0, 1, 2 and e = 0 .. 7 in that order; the 32 lanes by a butterfly (offsets 16, 8, 4,
+ * 2, 1); + b[i] last. */
+int bg_thin_contract(const void* a, int a_dtype, const float* w, const float* b, float* y, int M, int n, bg_stream_t stream);
+/* G * (s8 * 768 + 768 + s8) doubles, s8 = 8 ceil(s / 8), for the plan below; 0 for M <= 0 or s outside 1 .. 48. */
+size_t bg_thin_wgrad_workspace_bytes(int M, int s);
+/* g fp32 = t^T u: t [M, s] (t_dtype: any of the three, row stride ldt >= s), u [M, 768] 16-bit dense.  g is [s, 768], or [768, s]
+ * with g_transposed != 0 (an embed's dW0 = dH^T X in nn.Linear's layout).  colsum_of: 0 none (colsum NULL), 1 colsum [768] = column
+ * sums of u (db0), 2 colsum [s] = column sums of t (db3), from the same launch.  Plan, a pure function of (M, s): cap = 256 / ceil(s
+ * / 8) row workgroups at most, R = min(max(ceil(M / (8 cap)), 4), 64) rows per fp32 chain, chunks of 8 R rows, W = min(chunks, cap)
+ * row workgroups; a workgroup (w, 256-column slab, group of 8 k) takes the chunks w, w + W, ...; in chunk c half-wave h walks the rows
+ * c 8 R + 8 i + h, i = 0 .. R - 1, with acc = fma(t[m, k], u[m, c], acc) per (k, column); the eight chains of a chunk are added in order of h in fp64 into the
+ * workgroup's fp64 sum (a column sum: fp32 chains acc += value of 8 rows, i = 8 j .. 8 j + 7, folded in order into the half-wave's
+ * fp64 sum, then the eight half-waves in order of h), which goes to the workspace; a second kernel adds
+ * the W partials in index order in fp64 and rounds once.  A workspace smaller than bg_thin_wgrad_workspace_bytes is BG_E_ARG.  A
+ * non-finite u[m, c] reaches column c of g alone, a non-finite t[m, k] row k alone. */
+int bg_thin_wgrad(const void* t, int t_dtype, int ldt, const void* u, int u_dtype, float* g, int g_transposed, float* colsum,
+                  int colsum_of, int M, int s, void* workspace, size_t workspace_bytes, bg_stream_t stream);
+/* h = SiLU(LayerNorm(x)) over 768 columns in one pass, SiLU(v) = v / (1 + expf(-v)) in fp32, and stats as bg_ln_train_fwd writes
+ * them: the same row kernel (csrc/ln_rows.h), dtype pairs, layout and checks. */
+int bg_ln_silu_train_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* h, int h_dtype, float* stats, int M,
+                         float eps, bg_stream_t stream);
+/* = bg_ln_bwd_workspace_bytes(M) */
+size_t bg_ln_silu_bwd_workspace_bytes(int M);
+/* The backward of the above: v = xhat * gamma + beta recomputed from x and stats as the forward formed it, sg = 1 / (1 + expf(-v)),
+ * dv = dh * (sg + v * sg * (1 - sg)), then bg_ln_bwd's pass with dv in dy's place (no dskip): dx, and dgamma / dbeta through the
+ * same chains, workspace and fp64 merge. */
+int bg_ln_silu_bwd(const void* dh, int h_dtype, const void* x, int x_dtype, const float* stats, const float* gamma, const float* beta,
+                   void* dx, float* dgamma, float* dbeta, int M, void* workspace, size_t workspace_bytes, bg_stream_t stream);
+/* The gradient of bg_masked_mse's mean: dpred fp32 [rows, ld], every element written --
+ *     (pred - target) * coef,  coef = (2 * g[0]) / (out3[2] * (float)ncols)  in fp32
+ * in columns [col0, col0 + ncols) of rows with row_mask == 0, exactly 0 elsewhere (a select: NaN / Inf there is not read).  out3:
+ * bg_masked_mse's output of the same call (out3[2] = valid rows, read on the device); g: the upstream gradient, a device scalar (it
+ * carries a GradScaler's scale).  No valid row: all zeros.  One launch, nothing is read back. */
+int bg_masked_mse_bwd(const float* pred, const float* target, const uint8_t* row_mask, long long rows, int ld, int col0, int ncols,
+                      const float* out3, const float* g, float* dpred, bg_stream_t stream);
+
 /* QKV projection with the LayerNorm fold + self-attention in ONE launch (csrc/qkv_attn.hip): sequences of an even length
  * N <= 64, all B of them equally long; key_pad (may be NULL) as bg_attn_fwd's.  x_hi [B*N, 768] raw 16-bit rows, w_qkv [2304, 768] /
  * bias / colsum as bg_gemm_ex_fwd's fold operands, stats_in [12][B*N][2] the row statistics partials of x; out [B*N, 768] = what
