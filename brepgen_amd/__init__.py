@@ -15,6 +15,9 @@ Drop-in for the reference's call surface on that path only:
     nn.Linear of the encoder layers under autocast (forward, dX, dW + db) (linear.py) -> bg_weight_cast / bg_gemm_ex_fwd / bg_linear_wgrad
     nn.LayerNorm, ReLU, nn.Dropout and the residual adds of the encoder layers in net.train() (layer.py) -> bg_ln_train_fwd / bg_ln_bwd / bg_dropout_add_fwd / bg_relu_dropout_fwd
     the denoisers' embed MLPs / time_embed / fc_out and the masked-MSE loss in training (mlp.py, training.mse_loss) -> bg_thin_expand / bg_thin_contract / bg_thin_wgrad / bg_ln_silu_train_fwd / bg_ln_silu_bwd / bg_masked_mse_bwd
+    the VAEs' ResnetBlock2D in training: GroupNorm + SiLU + 3x3 conv forward, dX, dW + db, GroupNorm backward (conv.py) -> bg_conv_wgrad / bg_conv_weight_pack / bg_gn_act_bwd + the VAE forward entries
+      (not built: the rest of the VAE backward -- up-sampling / stride-2 convolutions, conv_in / conv_out, mid-block attention, the 1-D
+      blocks and resamplers, the posterior, a whole-VAE training step)
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from . import optim  # noqa: F401
@@ -58,6 +61,9 @@ __all__ += list(_LAYER)
 _MLP = ("thin_linear_in", "thin_linear_out", "ln_silu", "DeviceMLP", "use_device_mlps")
 _TRAINING = ("mse_loss", "use_device_training")
 __all__ += list(_MLP + _TRAINING)
+# the VAEs' ResnetBlock2D in training: GroupNorm + activation + convolution, forward and backward on the device (conv.py)
+_CONV = ("gn_act_conv", "DeviceResnetBlock2D", "use_device_resnets")
+__all__ += list(_CONV)
 
 
 def __getattr__(name):
@@ -91,4 +97,7 @@ def __getattr__(name):
     if name in _TRAINING:
         from . import training
         return getattr(training, name)
+    if name in _CONV:
+        from . import conv
+        return getattr(conv, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

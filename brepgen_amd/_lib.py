@@ -214,6 +214,12 @@ _SIGNATURES = {
     "bg_ln_silu_bwd_workspace_bytes": (C.c_size_t, [C.c_int]),
     "bg_ln_silu_bwd": (C.c_int, [vp, C.c_int, vp, C.c_int, fp, fp, fp, vp, fp, fp, C.c_int, vp, C.c_size_t, vp]),
     "bg_masked_mse_bwd": (C.c_int, [fp, fp, u8p, C.c_longlong, C.c_int, C.c_int, C.c_int, fp, fp, fp, vp]),
+    "bg_conv_wgrad": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp] + [C.c_int] * 10 + [vp, C.c_size_t, vp]),
+    "bg_conv_wgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 8),
+    "bg_conv_wgrad_split": (C.c_int, [C.c_int] * 7),
+    "bg_conv_weight_pack": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "bg_gn_act_bwd_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "bg_gn_act_bwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

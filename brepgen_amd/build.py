@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbrepgen_hip.so")
-SOURCES = ["elementwise.hip", "embed.hip", "gemm_f32.hip", "gemm_16bit.hip", "gemm_p256.hip", "gemm_split.hip", "qkv_attn.hip", "ffn_fused.hip", "out_tail.hip", "attn.hip", "attn_train.hip", "linear_bwd.hip", "layer_train.hip", "mlp_train.hip", "vae.hip", "dedup.hip", "hash_dedup.hip", "chamfer.hip", "metrics.hip", "mesh_sample.hip", "batch.hip", "rng.hip", "vae_loss.hip", "optim.hip", "compact.hip", "vae_exec.hip", "collective.hip", "denoiser.hip", "runtime.hip"]
+SOURCES = ["elementwise.hip", "embed.hip", "gemm_f32.hip", "gemm_16bit.hip", "gemm_p256.hip", "gemm_split.hip", "qkv_attn.hip", "ffn_fused.hip", "out_tail.hip", "attn.hip", "attn_train.hip", "linear_bwd.hip", "conv_train.hip", "layer_train.hip", "mlp_train.hip", "vae.hip", "dedup.hip", "hash_dedup.hip", "chamfer.hip", "metrics.hip", "mesh_sample.hip", "batch.hip", "rng.hip", "vae_loss.hip", "optim.hip", "compact.hip", "vae_exec.hip", "collective.hip", "denoiser.hip", "runtime.hip"]
 PER_FILE_FLAGS = {}
 # -fno-slp-vectorize: hipcc's SLP vectoriser turns adjacent scalar fp32 arithmetic into PACKED fp32 VALU instructions with op_sel broadcast
 # modifiers (v_pk_add_f32 ... op_sel_hi:[1,0], v_pk_mul_f32 ... op_sel:[0,1]).  On gfx950 (ROCm 7.2) a wave executing those returns WRONG values

@@ -1,0 +1,523 @@
+// The backward of a VAE ResnetBlock2D's convolution layer, y = conv(act(GroupNorm(x))) + b (stride 1, 'same' zero padding, odd window):
+//   bg_conv_wgrad        dw[n, tap, c] = sum_{s,y,x} dy[s,y,x,n] a[s, y + ky - kh/2, x + kx - kw/2, c]  and  db[n] = sum dy[., n]
+//   bg_conv_weight_pack  the nn.Conv weight [N, C, kh, kw] -> the forward pack [N, kh*kw*C] and / or the data-gradient pack
+//                        [C, kh*kw*N] with the taps reversed, 16-bit, one launch
+//   bg_gn_act_bwd        the backward of a = act(GroupNorm(x)): dx (+ dskip), dgamma, dbeta
+// The data gradient needs no kernel of its own: a 'same' forward convolution of dy with the reversed-tap pack is it, so it runs on
+// bg_conv_gemm_fwd / bg_im2col + bg_gemm_bias_act_fwd as the forward does.
+//
+// Weight gradient (cw_wgrad_kernel).  This is lb_wgrad_kernel's organisation (linear_bwd.hip): a workgroup of four waves owns one
+// 128 x 128 tile of dw [N, K = kh*kw*C] and one contiguous slice of the M = S*H*W output pixels, walked in steps of 32 rows through
+// two row-major LDS images read by the hardware transpose read, one barrier per step, the bias gradient from the staged dY values,
+// slices combined through an fp32 workspace by lb_reduce_kernel.  The one difference is the second operand's loader.  With
+// C % 128 == 0 a 128-column K tile lies inside ONE tap (ky, kx), so the row the loader stages for output pixel m = (s, y, x) is the
+// activation pixel (s, y + ky - kh/2, x + kx - kw/2): row m + (ky - kh/2) W + (kx - kw/2) of `a`, or zeros -- filled in registers,
+// never read -- when the shifted pixel leaves the H x W grid of sample s.  A shifted row therefore never comes from a neighbouring
+// sample, and the kh*kw-fold im2col matrix is never written.  lb_wgrad_kernel keeps its own copy of the tile body: hoisting it into
+// the helpers of wgrad_tile.h changed that kernel's register allocation and schedule, and its instruction stream is what round 14
+// measured.
+//
+// GroupNorm + activation backward.  With xh = (x - mean) rstd, v = gamma xh + beta, dv = da act'(v):
+//     dgamma[c] = sum_{s,p} dv xh,   dbeta[c] = sum_{s,p} dv,
+//     dx = rstd (dv gamma - m1 - xh m2) [+ dskip],   m1 = mean_group(dv gamma),  m2 = mean_group(dv gamma xh)
+// (the means over the P positions x C/G channels of the element's (sample, group)); xh is formed with the statistics' mean corrected
+// by its fp64-measured error (gb_finish_kernel).  Pass 1 (gb_sums_kernel) writes the per-(sample,
+// channel) sums of dv and dv xh over chunks of 64 positions, in fp64.
+// gb_finish_kernel adds the chunks in fp64 in index order and forms m1 / m2 per (sample, group); gb_param_kernel adds the samples
+// in fp64 into dgamma / dbeta; pass 2 (gb_dx_kernel) recomputes dv and writes dx.  16-byte accesses throughout.
+#include "wgrad_tile.h"
+#include <math.h>
+
+namespace bg {
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// weight gradient
+// ---------------------------------------------------------------------------------------------------------------------------------
+// OUT: 0 = fp32 partial tile to the workspace (split > 1), 1 = dw / db in fp32, 2 = dw / db in the operand dtype
+template <bool F16, int OUT>
+__global__ __launch_bounds__(256, 2) void cw_wgrad_kernel(const void* __restrict__ dy_, int ld_dy, const void* __restrict__ a_, int ld_a,
+                                                          void* __restrict__ dw_, void* __restrict__ db_, int M, int N, int C, int kh,
+                                                          int kw, int lh, int lw, int slice_rows) {
+    using T = typename Elem<F16>::T;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[4 * LB_IMG];      // [stage][dY image | activation image]
+    const T* __restrict__ dy = reinterpret_cast<const T*>(dy_);
+    const T* __restrict__ a = reinterpret_cast<const T*>(a_);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave >> 1, wk = wave & 1;
+    // lb_wgrad_kernel's XCD-aware walk: K tile fastest, then N tile, then slice; the K tiles of a tap share a dY piece AND (shifted by
+    // less than a grid row or two) the activation rows, so the whole run of an XCD works out of one L2
+    const int lid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    const int K = kh * kw * C;
+    const int kt_n = K >> 7, nt_n = N >> 7;
+    const int kt = lid % kt_n, nt = (lid / kt_n) % nt_n, slice = lid / (kt_n * nt_n);
+    const int k0 = kt * 128, n0 = nt * 128;
+    const int m_begin = slice * slice_rows;              // (a forced split beyond the row steps: trailing slices are empty, zero partials)
+    const int m_end = min(M, m_begin + slice_rows);
+    const int nsteps = m_end > m_begin ? (m_end - m_begin + LB_RS - 1) / LB_RS : 0;
+    const bool with_db = db_ != nullptr && kt == 0;
+
+    // the tap of this K tile (C % 128 == 0: one tap per tile) and its shift on the H x W grid
+    const int tap = k0 / C, c0 = k0 - tap * C;
+    const int oy = tap / kw - (kh >> 1), ox = tap % kw - (kw >> 1);
+    const int H = 1 << lh, W = 1 << lw;
+    const int shift = oy * W + ox;                      // rows of `a` between an output pixel and the pixel the tap reads
+
+    // ---- staging: thread = (16-byte chunk sc, rows sr and sr + 16) of both 32 x 128 pieces ----
+    const int sc = tid & 15, sr = tid >> 4;
+    const T* dyp = dy + n0 + sc * 8;
+    const T* ap = a + c0 + sc * 8;
+    const unsigned st_off = lb_off(sr, sc);            // row sr + 16 has the same swizzle term: + 16 * 256 bytes
+    uint4 rdy[2], ra[2];
+    float dbacc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dbacc[e] = 0.f;
+    auto fetch = [&](int it) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int m = m_begin + it * LB_RS + sr + 16 * j;
+            rdy[j] = make_uint4(0u, 0u, 0u, 0u);
+            ra[j] = make_uint4(0u, 0u, 0u, 0u);
+            if (m < m_end) {
+                rdy[j] = *reinterpret_cast<const uint4*>(dyp + (size_t)m * ld_dy);
+                const int x = m & (W - 1), y = (m >> lw) & (H - 1);
+                // inside the sample's own grid: row m + shift is then a pixel of the same sample, 0 <= m + shift < M
+                if ((unsigned)(y + oy) < (unsigned)H && (unsigned)(x + ox) < (unsigned)W)
+                    ra[j] = *reinterpret_cast<const uint4*>(ap + (size_t)(m + shift) * ld_a);
+            }
+        }
+    };
+    auto stash = [&](int st) {
+        unsigned char* img = lds + st * 2 * LB_IMG + st_off;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            *reinterpret_cast<uint4*>(img + j * 16 * 256) = rdy[j];
+            *reinterpret_cast<uint4*>(img + LB_IMG + j * 16 * 256) = ra[j];
+        }
+        if (with_db) {
+            lb_add8<F16>(dbacc, rdy[0]);
+            lb_add8<F16>(dbacc, rdy[1]);
+        }
+    };
+
+    unsigned a_off[2][2], b_off[2][2];
+    lb_frag_offsets(lane, wn, wk, a_off, b_off);
+    f32x16 acc[2][2];
+    lb_zero(acc);
+
+    if (nsteps > 0) {
+        fetch(0);
+        stash(0);
+    }
+    for (int it = 0; it < nsteps; ++it) {
+        const int st = it & 1;
+        const bool more = it + 1 < nsteps;
+        if (more) fetch(it + 1);
+        __syncthreads();                                  // stage st is written; everybody is done reading stage st ^ 1
+        lb_step<F16>(lds + st * 2 * LB_IMG, a_off, b_off, acc);
+        if (more) stash(st ^ 1);
+    }
+
+    lb_store_tile<F16, OUT>(acc, dw_, OUT == 0 ? (size_t)slice * N * K : 0, K, n0 + 64 * wn, k0 + 64 * wk, lane);
+    if (with_db) lb_store_db<F16, OUT>(dbacc, lds, db_, (OUT == 0 ? (size_t)slice * N : 0) + n0, tid);
+}
+
+template <bool F16>
+static void cw_launch(hipStream_t s, const void* dy, int ld_dy, const void* a, int ld_a, void* dw, void* db, int M, int N, int C, int kh,
+                      int kw, int lh, int lw, bool out16, int S, float* ws) {
+    const int K = kh * kw * C;
+    const dim3 grid((unsigned)((K / 128) * (N / 128) * S));      // one workgroup per (K tile, N tile, slice)
+    const int slice_rows = lb_slice_rows(M, S);
+    if (S > 1) {
+        hipLaunchKernelGGL((cw_wgrad_kernel<F16, 0>), grid, dim3(256), 0, s, dy, ld_dy, a, ld_a, (void*)ws, (void*)(ws + (size_t)S * N * K), M, N,
+                           C, kh, kw, lh, lw, slice_rows);
+        lb_reduce(s, F16, out16, ws, dw, db, S, N, K);
+    } else if (out16) {
+        hipLaunchKernelGGL((cw_wgrad_kernel<F16, 2>), grid, dim3(256), 0, s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, slice_rows);
+    } else {
+        hipLaunchKernelGGL((cw_wgrad_kernel<F16, 1>), grid, dim3(256), 0, s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, slice_rows);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// weight pack: a workgroup takes a 32 (n) x 32 (c) x kh*kw block of the weight through LDS.  The source block is 32 runs of
+// 32 * kh*kw consecutive elements; both outputs leave in 16-byte pieces (64-byte runs).
+// MODE: 0 = 16-bit source (bits copied), 1 = fp32 -> bf16, 2 = fp32 -> fp16
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int CP_MAX_TAPS = 25;
+template <int MODE>
+__global__ __launch_bounds__(256) void cw_pack_kernel(const void* __restrict__ src_, void* __restrict__ fwd_, void* __restrict__ dgrad_,
+                                                      int N, int C, int T) {
+    __shared__ __attribute__((aligned(16))) unsigned short tile[32 * 32 * CP_MAX_TAPS];      // [n][c][t], as in the source
+    const int tid = threadIdx.x;
+    const int c0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
+    const int run = 32 * T;                               // consecutive source elements per n
+    for (int i = tid; i < 32 * run; i += 256) {
+        const int n = i / run, r = i - n * run;
+        const size_t at = ((size_t)(n0 + n) * C + c0) * T + r;
+        unsigned short v;
+        if (MODE == 0) v = reinterpret_cast<const unsigned short*>(src_)[at];
+        else if (MODE == 1) { union { __bf16 b; unsigned short u; } c; c.b = (__bf16)reinterpret_cast<const float*>(src_)[at]; v = c.u; }
+        else { union { _Float16 h; unsigned short u; } c; c.h = cvt16<_Float16>(reinterpret_cast<const float*>(src_)[at]); v = c.u; }
+        tile[i] = v;
+    }
+    __syncthreads();
+    // item = (row of the 32 x T output block, 8-element piece q of its 32 columns)
+    for (int i = tid; i < 32 * T * 4; i += 256) {
+        const int q = i & 3, t = (i >> 2) % T, r = (i >> 2) / T;
+        if (fwd_) {                                        // fwd[n0 + r][t][c0 + 8 q ..]
+            unsigned short e[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) e[k] = tile[(r * 32 + 8 * q + k) * T + t];
+            uint4 v;
+            v.x = e[0] | ((unsigned)e[1] << 16); v.y = e[2] | ((unsigned)e[3] << 16);
+            v.z = e[4] | ((unsigned)e[5] << 16); v.w = e[6] | ((unsigned)e[7] << 16);
+            *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(fwd_) + ((size_t)(n0 + r) * T + t) * C + c0 + 8 * q) = v;
+        }
+        if (dgrad_) {                                      // dgrad[c0 + r][T - 1 - t][n0 + 8 q ..]
+            unsigned short e[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) e[k] = tile[((8 * q + k) * 32 + r) * T + t];
+            uint4 v;
+            v.x = e[0] | ((unsigned)e[1] << 16); v.y = e[2] | ((unsigned)e[3] << 16);
+            v.z = e[4] | ((unsigned)e[5] << 16); v.w = e[6] | ((unsigned)e[7] << 16);
+            *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(dgrad_) + ((size_t)(c0 + r) * T + (T - 1 - t)) * N + n0 + 8 * q) = v;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// GroupNorm + activation backward
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int GB_CHUNK = 64;              // positions per chunk (one workgroup)
+
+// act'(v): the derivative of what bg_im2col's act_apply computes (vae.hip)
+template <int ACT> __device__ __forceinline__ float gb_dact(float v) {
+    if (ACT == 1) {
+        const float sg = 1.0f / (1.0f + __expf(-v));
+        return sg * (1.0f + v * (1.0f - sg));
+    }
+    if (ACT == 2) return 0.5f * (1.0f + erff(v * 0.70710678118654752f)) + v * (0.39894228040143268f * __expf(-0.5f * v * v));
+    return 1.0f;
+}
+
+// (mean, rstd) of the four channels 4 j .. 4 j + 3 of sample s
+__device__ __forceinline__ void gb_stats4(const float* __restrict__ stats, int s, int G, int cpg, int j, float (&mean)[4], float (&rstd)[4]) {
+    if ((cpg & 3) == 0) {
+        const float2 st = *reinterpret_cast<const float2*>(stats + ((size_t)s * G + (4 * j) / cpg) * 2);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { mean[e] = st.x; rstd[e] = st.y; }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float2 st = *reinterpret_cast<const float2*>(stats + ((size_t)s * G + (4 * j + e) / cpg) * 2);
+            mean[e] = st.x; rstd[e] = st.y;
+        }
+    }
+}
+
+// xc = x - mean, xh = (xc - delta) * rstd and dv of four channels of one position.  delta: the statistics' mean error (below); 0 in pass 1
+template <int ACT>
+__device__ __forceinline__ void gb_elem4(float4 x, float4 da, const float (&mean)[4], const float (&rstd)[4], const float (&delta)[4], float4 ga,
+                                         float4 be, float (&xc)[4], float (&xh)[4], float (&dv)[4]) {
+    const float xs[4] = {x.x, x.y, x.z, x.w}, ds[4] = {da.x, da.y, da.z, da.w};
+    const float gs[4] = {ga.x, ga.y, ga.z, ga.w}, bs[4] = {be.x, be.y, be.z, be.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        xc[e] = xs[e] - mean[e];
+        xh[e] = (xc[e] - delta[e]) * rstd[e];
+        dv[e] = ds[e] * gb_dact<ACT>(xh[e] * gs[e] + bs[e]);
+    }
+}
+
+// pass 1: part[s][chunk][0][c] = sum_p dv, [1][c] = sum_p dv xh, [2][c] = sum_p (x - mean) over the chunk's positions.  grid (chunks, S).
+// Thread (r, j) of R = max(1, 256 / (C / 4)) position rows x C / 4 column quads adds positions p0 + r, p0 + r + R, ... of the chunk, then
+// the R chains of a column are added in order of r.  Sums and products are fp64 from the first term (dv and xh are fp32 values): with
+// fp32 chains of 32 positions the dgamma of [2, 64, 512] missed the tests' 2 x torch yardstick (7.3e-6 against 2 x 3.4e-6), and the pass
+// stays bound by its two fp32 streams.
+template <int ACT>
+__global__ __launch_bounds__(256) void gb_sums_kernel(const float* __restrict__ da, const float* __restrict__ x, const float* __restrict__ stats,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta, double* __restrict__ part,
+                                                      int P, int C, int G) {
+    __shared__ double red[256 * 12];
+    const int tid = threadIdx.x, chunk = blockIdx.x, s = blockIdx.y, nchunk = gridDim.x;
+    const int c4n = C >> 2, cpg = C / G;
+    const int R = c4n >= 256 ? 1 : 256 / c4n;
+    const int r = c4n >= 256 ? 0 : tid / c4n;
+    const int p0 = chunk * GB_CHUNK, p1 = min(P, p0 + GB_CHUNK);
+    const size_t base = (size_t)s * P * C;
+    double* out = part + ((size_t)s * nchunk + chunk) * 3 * C;
+    const bool active = r < R;
+    for (int j = c4n >= 256 ? tid : tid - r * c4n; active && j < c4n; j += 256) {
+        float mean[4], rstd[4];
+        gb_stats4(stats, s, G, cpg, j, mean, rstd);
+        const float4 ga = *reinterpret_cast<const float4*>(gamma + 4 * j);
+        const float4 be = *reinterpret_cast<const float4*>(beta + 4 * j);
+        const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+        double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0}, s3[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int p = p0 + r; p < p1; p += R) {
+            const size_t at = base + (size_t)p * C + 4 * j;
+            float xc[4], xh[4], dv[4];
+            gb_elem4<ACT>(*reinterpret_cast<const float4*>(x + at), *reinterpret_cast<const float4*>(da + at), mean, rstd, zero, ga, be, xc, xh, dv);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)dv[e];
+                s1[e] += d;
+                s2[e] = fma(d, (double)xh[e], s2[e]);     // the product of two fp32 values is exact in fp64
+                s3[e] += (double)xc[e];
+            }
+        }
+        if (R == 1) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                out[4 * j + e] = s1[e];
+                out[C + 4 * j + e] = s2[e];
+                out[2 * C + 4 * j + e] = s3[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                red[tid * 12 + e] = s1[e];
+                red[tid * 12 + 4 + e] = s2[e];
+                red[tid * 12 + 8 + e] = s3[e];
+            }
+        }
+    }
+    if (R > 1) {                                          // (uniform over the workgroup)
+        __syncthreads();
+        if (tid < c4n) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) {
+                double v = red[tid * 12 + e];
+                for (int q = 1; q < R; ++q) v += red[(q * c4n + tid) * 12 + e];
+                out[(e >> 2) * C + 4 * tid + (e & 3)] = v;
+            }
+        }
+    }
+}
+
+// sums[s][0 | 1 | 2][c] = the chunks of part in index order (fp64); means[s][g] = (m1, m2, delta, 0).  One workgroup per sample.
+// delta = mean_group(x - mean): what the fp32 statistics' mean is off by (a few ulp of |mean|: with |mean| = 50 std that is 1e-5 std, more
+// than everything else in this backward together).  Pass 1 ran without it, so its second sum is corrected here to first order,
+// sum dv xh_true = sum dv xh - delta rstd sum dv; pass 2 subtracts delta itself.
+__global__ __launch_bounds__(256) void gb_finish_kernel(const double* __restrict__ part, const float* __restrict__ stats,
+                                                        const float* __restrict__ gamma, double* __restrict__ sums, float* __restrict__ means,
+                                                        int nchunk, int P, int C, int G) {
+    const int tid = threadIdx.x, s = blockIdx.x;
+    const double* in = part + (size_t)s * nchunk * 3 * C;
+    double* out = sums + (size_t)s * 3 * C;
+    for (int i = tid; i < 3 * C; i += 256) {
+        double v = in[i];
+        for (int ch = 1; ch < nchunk; ++ch) v += in[(size_t)ch * 3 * C + i];
+        out[i] = v;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const int cpg = C / G;
+    const double inv = 1.0 / ((double)P * cpg);
+    for (int g = tid; g < G; g += 256) {
+        double sx = 0.0;
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c) sx += out[2 * C + c];
+        const float delta = (float)(sx * inv);
+        const double dr = (double)delta * (double)stats[((size_t)s * G + g) * 2 + 1];
+        double m1 = 0.0, m2 = 0.0;
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+            const double ga = (double)gamma[c];
+            const double s2 = out[C + c] - dr * out[c];
+            out[C + c] = s2;
+            m1 += ga * out[c];
+            m2 += ga * s2;
+        }
+        *reinterpret_cast<float4*>(means + ((size_t)s * G + g) * 4) = make_float4((float)(m1 * inv), (float)(m2 * inv), delta, 0.f);
+    }
+}
+
+// dbeta[c] = sum_s sums[s][0][c], dgamma[c] = sum_s sums[s][1][c]: a workgroup takes 64 channels; thread (q, c) adds the samples of
+// quarter q in index order in fp64, the four quarters are added in order.
+__global__ __launch_bounds__(256) void gb_param_kernel(const double* __restrict__ sums, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                       int S, int C) {
+    __shared__ double red[2][256];
+    const int tid = threadIdx.x, cl = tid & 63, q = tid >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const int per = (S + 3) / 4, s0 = q * per, s1 = min(S, s0 + per);
+    double vb = 0.0, vg = 0.0;
+    if (c < C)
+        for (int s = s0; s < s1; ++s) {
+            vb += sums[(size_t)s * 3 * C + c];
+            vg += sums[(size_t)s * 3 * C + C + c];
+        }
+    red[0][tid] = vb;
+    red[1][tid] = vg;
+    __syncthreads();
+    if (q == 0 && c < C) {
+        dbeta[c] = (float)(((red[0][cl] + red[0][64 + cl]) + red[0][128 + cl]) + red[0][192 + cl]);
+        dgamma[c] = (float)(((red[1][cl] + red[1][64 + cl]) + red[1][128 + cl]) + red[1][192 + cl]);
+    }
+}
+
+// pass 2: dx = rstd * fma(-xh, m2, fma(dv, gamma, -m1)) [+ dskip].  One thread per four channels of one position, grid-strided.
+template <int ACT>
+__global__ __launch_bounds__(256) void gb_dx_kernel(const float* __restrict__ da, const float* __restrict__ x, const float* __restrict__ stats,
+                                                    const float* __restrict__ means, const float* __restrict__ gamma,
+                                                    const float* __restrict__ beta, const float* __restrict__ dskip, float* __restrict__ dx,
+                                                    size_t total4, unsigned n4s, int C, int G) {
+    const int c4n = C >> 2, cpg = C / G;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
+        const int s = (int)(i / n4s);
+        const int j = (int)(i % (unsigned)c4n);
+        float mean[4], rstd[4], delta[4], m1[4], m2[4], xc[4], xh[4], dv[4];
+        gb_stats4(stats, s, G, cpg, j, mean, rstd);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float4 m = *reinterpret_cast<const float4*>(means + ((size_t)s * G + (4 * j + e) / cpg) * 4);
+            m1[e] = m.x; m2[e] = m.y; delta[e] = m.z;
+        }
+        const float4 ga = *reinterpret_cast<const float4*>(gamma + 4 * j);
+        const float4 be = *reinterpret_cast<const float4*>(beta + 4 * j);
+        gb_elem4<ACT>(reinterpret_cast<const float4*>(x)[i], reinterpret_cast<const float4*>(da)[i], mean, rstd, delta, ga, be, xc, xh, dv);
+        const float gs[4] = {ga.x, ga.y, ga.z, ga.w};
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = rstd[e] * fmaf(-xh[e], m2[e], fmaf(dv[e], gs[e], -m1[e]));
+        if (dskip) {
+            const float4 d = reinterpret_cast<const float4*>(dskip)[i];
+            o[0] += d.x; o[1] += d.y; o[2] += d.z; o[3] += d.w;
+        }
+        reinterpret_cast<float4*>(dx)[i] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+static inline int gb_chunks(int P) { return (P + GB_CHUNK - 1) / GB_CHUNK; }
+static inline bool gb_shape_ok(int S, int P, int C, int G) {
+    return S >= 1 && S <= 65535 && P >= 1 && C >= 4 && C % 4 == 0 && G >= 1 && C % G == 0 && (long long)S * P * C < (1ll << 40) &&
+           (long long)P * (C / 4) < (1ll << 32);
+}
+
+static inline int cw_log2(int v) {
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return (v > 0 && (1 << l) == v) ? l : -1;
+}
+static inline bool cw_shape_ok(int S, int H, int W, int N, int C, int kh, int kw) {
+    return S >= 0 && cw_log2(H) >= 0 && cw_log2(W) >= 0 && N >= 128 && C >= 128 && N % 128 == 0 && C % 128 == 0 && kh >= 1 && kw >= 1 &&
+           kh <= 5 && kw <= 5 && (kh & 1) && (kw & 1) && (long long)S * H * W < (1ll << 31) - 4096 && (long long)N * kh * kw * C < (1ll << 31);
+}
+
+}  // namespace bg
+
+using namespace bg;
+
+extern "C" int bg_conv_wgrad_split(int S, int H, int W, int N, int C, int kh, int kw) {
+    if (!cw_shape_ok(S, H, W, N, C, kh, kw) || S == 0) return 1;
+    return lb_auto_split(S * H * W, N, kh * kw * C);
+}
+
+extern "C" size_t bg_conv_wgrad_workspace_bytes(int S, int H, int W, int N, int C, int kh, int kw, int split) {
+    if (!cw_shape_ok(S, H, W, N, C, kh, kw) || S == 0 || split < 0 || split > LB_MAX_SPLIT) return 0;
+    const int K = kh * kw * C;
+    return lb_workspace(N, K, split == 0 ? lb_auto_split(S * H * W, N, K) : split);
+}
+
+extern "C" int bg_conv_wgrad(const void* dy, int ld_dy, const void* a, int ld_a, void* dw, void* db, int S, int H, int W, int N, int C,
+                             int kh, int kw, int dtype, int out_dtype, int split, void* workspace, size_t workspace_bytes,
+                             bg_stream_t stream) {
+    BG_REQUIRE(dtype == BG_BF16 || dtype == BG_F16, BG_E_DTYPE, "bg_conv_wgrad: operand dtype %d (BG_BF16 or BG_F16)", dtype);
+    BG_REQUIRE(out_dtype == BG_F32 || out_dtype == dtype, BG_E_DTYPE, "bg_conv_wgrad: out_dtype %d is neither BG_F32 nor the operand dtype %d",
+               out_dtype, dtype);
+    BG_REQUIRE(S >= 0 && cw_log2(H) >= 0 && cw_log2(W) >= 0 && (long long)S * H * W < (1ll << 31) - 4096, BG_E_SHAPE,
+               "bg_conv_wgrad: S = %d samples of an H = %d x W = %d grid (powers of two, fewer than 2^31 pixels)", S, H, W);
+    BG_REQUIRE(kh >= 1 && kw >= 1 && kh <= 5 && kw <= 5 && (kh & 1) && (kw & 1), BG_E_SHAPE,
+               "bg_conv_wgrad: window %d x %d (odd, each at most 5)", kh, kw);
+    BG_REQUIRE(N >= 128 && C >= 128 && N % 128 == 0 && C % 128 == 0 && (long long)N * kh * kw * C < (1ll << 31), BG_E_SHAPE,
+               "bg_conv_wgrad: N = %d and C = %d must be multiples of 128", N, C);
+    BG_REQUIRE(split >= 0 && split <= LB_MAX_SPLIT, BG_E_ARG, "bg_conv_wgrad: split = %d outside [0, %d] (0 = auto)", split, LB_MAX_SPLIT);
+    BG_REQUIRE(dw != nullptr, BG_E_ARG, "bg_conv_wgrad: null pointer (dw)");
+    BG_REQUIRE(S == 0 || (dy != nullptr && a != nullptr), BG_E_ARG, "bg_conv_wgrad: null pointer (dy, a)");
+    BG_REQUIRE(ld_dy >= N && ld_a >= C && ld_dy % 8 == 0 && ld_a % 8 == 0, BG_E_ALIGN,
+               "bg_conv_wgrad: pixel strides ld_dy = %d (>= N), ld_a = %d (>= C) must be multiples of 8 elements", ld_dy, ld_a);
+    BG_REQUIRE(aligned(dy, 16) && aligned(a, 16) && aligned(dw, 16) && aligned(db, 16) && aligned(workspace, 16), BG_E_ALIGN,
+               "bg_conv_wgrad: 16-byte alignment of dy / a / dw / db / workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const int K = kh * kw * C, M = S * H * W;
+    const size_t esz = out_dtype == BG_F32 ? 4 : 2;
+    if (M == 0) {
+        hipError_t e = hipMemsetAsync(dw, 0, (size_t)N * K * esz, s);
+        if (e == hipSuccess && db) e = hipMemsetAsync(db, 0, (size_t)N * esz, s);
+        BG_REQUIRE(e == hipSuccess, (int)e, "bg_conv_wgrad: hipMemsetAsync: %s", hipGetErrorString(e));
+        return 0;
+    }
+    const int SP = split == 0 ? lb_auto_split(M, N, K) : split;
+    const size_t need = lb_workspace(N, K, SP);
+    BG_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), BG_E_ARG,
+               "bg_conv_wgrad: workspace of %zu bytes, %zu needed for split = %d", workspace ? workspace_bytes : (size_t)0, need, SP);
+    const int lh = cw_log2(H), lw = cw_log2(W);
+    if (dtype == BG_F16) cw_launch<true>(s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, out_dtype != BG_F32, SP, (float*)workspace);
+    else cw_launch<false>(s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, out_dtype != BG_F32, SP, (float*)workspace);
+    return launch_status("conv_wgrad");
+}
+
+extern "C" int bg_conv_weight_pack(const void* src, int src_dtype, int N, int C, int kh, int kw, void* fwd, void* dgrad, int dtype,
+                                   bg_stream_t stream) {
+    BG_REQUIRE(dtype == BG_BF16 || dtype == BG_F16, BG_E_DTYPE, "bg_conv_weight_pack: target dtype %d (BG_BF16 or BG_F16)", dtype);
+    BG_REQUIRE(src_dtype == BG_F32 || src_dtype == dtype, BG_E_DTYPE,
+               "bg_conv_weight_pack: source dtype %d is neither BG_F32 nor the target dtype %d", src_dtype, dtype);
+    BG_REQUIRE(N >= 32 && C >= 32 && N % 32 == 0 && C % 32 == 0 && N / 32 <= 65535, BG_E_SHAPE,
+               "bg_conv_weight_pack: N = %d and C = %d must be multiples of 32", N, C);
+    BG_REQUIRE(kh >= 1 && kw >= 1 && kh <= 5 && kw <= 5 && (kh & 1) && (kw & 1) && (long long)N * C * kh * kw < (1ll << 31), BG_E_SHAPE,
+               "bg_conv_weight_pack: window %d x %d (odd, each at most 5)", kh, kw);
+    BG_REQUIRE(src != nullptr, BG_E_ARG, "bg_conv_weight_pack: null pointer (src)");
+    BG_REQUIRE(fwd != nullptr || dgrad != nullptr, BG_E_ARG, "bg_conv_weight_pack: null pointer (fwd and dgrad: at least one output)");
+    BG_REQUIRE(aligned(src, 16) && aligned(fwd, 16) && aligned(dgrad, 16), BG_E_ALIGN, "bg_conv_weight_pack: 16-byte alignment of src / fwd / dgrad");
+    const dim3 grid(C / 32, N / 32);
+    hipStream_t s = (hipStream_t)stream;
+    const int T = kh * kw;
+    if (src_dtype != BG_F32) hipLaunchKernelGGL(cw_pack_kernel<0>, grid, dim3(256), 0, s, src, fwd, dgrad, N, C, T);
+    else if (dtype == BG_BF16) hipLaunchKernelGGL(cw_pack_kernel<1>, grid, dim3(256), 0, s, src, fwd, dgrad, N, C, T);
+    else hipLaunchKernelGGL(cw_pack_kernel<2>, grid, dim3(256), 0, s, src, fwd, dgrad, N, C, T);
+    return launch_status("conv_weight_pack");
+}
+
+extern "C" size_t bg_gn_act_bwd_workspace_bytes(int S, int P, int C, int G) {
+    if (!gb_shape_ok(S, P, C, G)) return 0;
+    return al256((size_t)S * gb_chunks(P) * 3 * C * sizeof(double)) + al256((size_t)S * 3 * C * sizeof(double)) + al256((size_t)S * G * 4 * sizeof(float));
+}
+
+extern "C" int bg_gn_act_bwd(const float* da, const float* x, const float* stats, const float* gamma, const float* beta, const float* dskip,
+                             float* dx, float* dgamma, float* dbeta, int S, int P, int C, int G, int act, void* workspace,
+                             size_t workspace_bytes, bg_stream_t stream) {
+    BG_REQUIRE(S >= 1 && S <= 65535 && P >= 1 && (long long)S * P * C < (1ll << 40) && (long long)P * (C / 4) < (1ll << 32), BG_E_SHAPE,
+               "bg_gn_act_bwd: S = %d samples (1 .. 65535) of P = %d positions (>= 1)", S, P);
+    BG_REQUIRE(C >= 4 && C % 4 == 0 && G >= 1 && C % G == 0, BG_E_SHAPE, "bg_gn_act_bwd: C = %d must be a multiple of 4 and of G = %d", C, G);
+    BG_REQUIRE(act >= BG_VACT_NONE && act <= BG_VACT_GELU, BG_E_ARG, "bg_gn_act_bwd: act = %d (bg_vae_act)", act);
+    BG_REQUIRE(da && x && stats && gamma && beta && dx, BG_E_ARG, "bg_gn_act_bwd: null pointer (da, x, stats, gamma, beta, dx)");
+    BG_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), BG_E_ARG, "bg_gn_act_bwd: dgamma and dbeta: both or neither");
+    BG_REQUIRE(aligned(da, 16) && aligned(x, 16) && aligned(dskip, 16) && aligned(dx, 16) && aligned(gamma, 16) && aligned(beta, 16) &&
+                   aligned(stats, 8) && aligned(dgamma, 4) && aligned(dbeta, 4) && aligned(workspace, 16),
+               BG_E_ALIGN, "bg_gn_act_bwd: 16-byte alignment of da / x / dskip / dx / gamma / beta / workspace (stats: 8)");
+    const size_t need = bg_gn_act_bwd_workspace_bytes(S, P, C, G);
+    BG_REQUIRE(workspace != nullptr && workspace_bytes >= need, BG_E_ARG, "bg_gn_act_bwd: workspace of %zu bytes, %zu needed",
+               workspace ? workspace_bytes : (size_t)0, need);
+    hipStream_t s = (hipStream_t)stream;
+    const int nchunk = gb_chunks(P);
+    unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+    double* part = reinterpret_cast<double*>(ws);
+    double* sums = reinterpret_cast<double*>(ws + al256((size_t)S * nchunk * 3 * C * sizeof(double)));
+    float* means = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(sums) + al256((size_t)S * 3 * C * sizeof(double)));
+    const size_t total4 = (size_t)S * P * (C / 4);
+    const unsigned n4s = (unsigned)((size_t)P * (C / 4));
+    const unsigned blocks = (unsigned)((total4 + 255) / 256 < 65536 ? (total4 + 255) / 256 : 65536);
+    auto run = [&](auto A) {
+        constexpr int ACT = decltype(A)::value;
+        hipLaunchKernelGGL(gb_sums_kernel<ACT>, dim3(nchunk, S), dim3(256), 0, s, da, x, stats, gamma, beta, part, P, C, G);
+        hipLaunchKernelGGL(gb_finish_kernel, dim3(S), dim3(256), 0, s, (const double*)part, stats, gamma, sums, means, nchunk, P, C, G);
+        if (dgamma) hipLaunchKernelGGL(gb_param_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const double*)sums, dgamma, dbeta, S, C);
+        hipLaunchKernelGGL(gb_dx_kernel<ACT>, dim3(blocks), dim3(256), 0, s, da, x, stats, (const float*)means, gamma, beta, dskip, dx, total4,
+                           n4s, C, G);
+    };
+    if (act == BG_VACT_SILU) run(std::integral_constant<int, 1>{});
+    else if (act == BG_VACT_GELU) run(std::integral_constant<int, 2>{});
+    else run(std::integral_constant<int, 0>{});
+    return launch_status("gn_act_bwd");
+}

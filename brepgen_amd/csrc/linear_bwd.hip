@@ -23,42 +23,10 @@
 // Determinism.  No atomics, one writer per output element, fixed summation order.  With S > 1 slices each writes its fp32 partial
 // tile to the workspace ([S][N][K], then [S][N] for db) and lb_reduce_kernel adds the S partials in index order and writes dW / db in
 // the output dtype; with S = 1 the tile kernel writes dW / db itself.
-#include "gemm16.h"
+#include "wgrad_tile.h"
 #include <stdlib.h>
 
 namespace bg {
-
-typedef __attribute__((ext_vector_type(4))) short lb_v4s;
-
-constexpr int LB_RS = 32;                  // rows of M per step
-constexpr int LB_IMG = LB_RS * 256;        // one operand image: 32 rows x 128 16-bit columns
-constexpr int LB_MAX_SPLIT = 64;
-// AUTO split ("The Linear layers' backward"): aim for LB_TARGET_WGS tile x slice workgroups (two per CU), with at least
-// LB_MIN_STEPS row steps per slice
-constexpr int LB_TARGET_WGS = 512;
-constexpr int LB_MIN_STEPS = 8;
-
-// byte offset of 16-byte chunk ch (0..15) of image row `row`: the guide's dual-use image with plain 256-byte rows.  The sixteen
-// 16-byte slots a 32-lane half of a transpose read touches (4 rows x 4 chunks) fall on sixteen distinct slots of the 256-byte bank row
-__device__ __forceinline__ unsigned lb_off(int row, int ch) { return 256u * row + 16u * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-// eight consecutive rows of one column, as an MFMA fragment: rows r .. r + 3 from `p`, r + 4 .. r + 7 from `p4`
-template <bool F16> __device__ __forceinline__ typename Elem<F16>::V8 lb_frag(const unsigned char* p, const unsigned char* p4) {
-    union { lb_v4s s4[2]; typename Elem<F16>::V8 v; } u;
-    u.s4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) lb_v4s*)p);
-    u.s4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) lb_v4s*)p4);
-    return u.v;
-}
-
-template <bool F16> __device__ __forceinline__ void lb_add8(float (&acc)[8], uint4 v) {
-    float f[4];
-    unpack4_16<F16>(make_uint2(v.x, v.y), f);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += f[e];
-    unpack4_16<F16>(make_uint2(v.z, v.w), f);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[4 + e] += f[e];
-}
 
 // OUT: 0 = fp32 partial tile to the workspace (split > 1), 1 = dW / db in fp32, 2 = dW / db in the operand dtype
 template <bool F16, int OUT>
@@ -280,27 +248,15 @@ __global__ __launch_bounds__(256) void lb_cast_kernel(const void* __restrict__ s
     }
 }
 
-// ---- host-side plan ----
-static inline int lb_steps(int M) { return (M + LB_RS - 1) / LB_RS; }
-// rows per slice: whole row steps, the same for every slice but the last
-static inline int lb_slice_rows(int M, int S) { return ((lb_steps(M) + S - 1) / S) * LB_RS; }
-static inline bool lb_no_empty_slice(int M, int S) { return (long long)(S - 1) * lb_slice_rows(M, S) < (long long)M; }
+// ---- host-side plan: wgrad_tile.h ----
 static inline bool lb_shape_ok(int M, int N, int K) { return M >= 0 && N >= 128 && K >= 128 && N % 128 == 0 && K % 128 == 0; }
 
-static int lb_auto_split(int M, int N, int K) {
-    const int steps = lb_steps(M);
-    const long long tiles = (long long)(N / 128) * (K / 128);
-    long long S = LB_TARGET_WGS / tiles;
-    if (S > steps / LB_MIN_STEPS) S = steps / LB_MIN_STEPS;
-    if (S > LB_MAX_SPLIT) S = LB_MAX_SPLIT;
-    if (S < 1) S = 1;
-    while (S > 1 && !lb_no_empty_slice(M, (int)S)) --S;
-    return (int)S;
-}
-
-static size_t lb_workspace(int N, int K, int S) {
-    if (S <= 1) return 0;
-    return ((size_t)S * N * ((size_t)K + 1) * sizeof(float) + 255) & ~(size_t)255;
+void lb_reduce(hipStream_t s, bool f16, bool out16, const float* ws, void* dw, void* db, int S, int N, int K) {
+    const size_t nk = (size_t)N * K;
+    const unsigned blocks = (unsigned)((nk / 4 + N / 4 + 255) / 256);
+    with_bools(f16, out16, [&](auto F, auto O) {
+        hipLaunchKernelGGL((lb_reduce_kernel<decltype(F)::value, decltype(O)::value>), dim3(blocks), dim3(256), 0, s, ws, dw, db, S, nk, N);
+    });
 }
 
 template <bool F16>
@@ -314,9 +270,7 @@ static void lb_launch(hipStream_t s, const void* dy, int ld_dy, const void* x, i
         const size_t nk = (size_t)N * K;
         hipLaunchKernelGGL((lb_wgrad_kernel<F16, 0>), grid, dim3(256), 0, s, dy, ld_dy, x, ld_x, (void*)ws, (void*)(ws + (size_t)S * nk), M, N, K,
                            slice_rows, plain);
-        const unsigned blocks = (unsigned)((nk / 4 + N / 4 + 255) / 256);
-        if (out16) hipLaunchKernelGGL((lb_reduce_kernel<F16, true>), dim3(blocks), dim3(256), 0, s, (const float*)ws, dw, db, S, nk, N);
-        else hipLaunchKernelGGL((lb_reduce_kernel<F16, false>), dim3(blocks), dim3(256), 0, s, (const float*)ws, dw, db, S, nk, N);
+        lb_reduce(s, F16, out16, ws, dw, db, S, N, K);
     } else if (out16) {
         hipLaunchKernelGGL((lb_wgrad_kernel<F16, 2>), grid, dim3(256), 0, s, dy, ld_dy, x, ld_x, dw, db, M, N, K, slice_rows, plain);
     } else {

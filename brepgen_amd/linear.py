@@ -44,6 +44,36 @@ def _gemm(lib, a, w, bias, M, N, K):
     return out
 
 
+def linear_backward(x2, weight, dy, need_x, need_w, need_b, bias_dtype, split=0):
+    """The backward of y = x2 weight^T + bias for x2 [M, K] 16-bit and dy [M, N] (cast to x2's dtype): (dx [M, K] in x2's dtype,
+    dw [N, K], db [N]), each None unless asked for.  dw / db come out of ONE launch in one dtype -- the weight's when that is fp32
+    (the trainers' masters), otherwise x2's -- and db is cast to bias_dtype.  What `linear`'s autograd op runs; conv.py's 1x1
+    shortcut calls it too."""
+    lib = _lib.load()
+    N, K = weight.shape
+    M = x2.shape[0]
+    dx = dw = db = None
+    with torch.autocast(device_type="cuda", enabled=False):
+        dy = dy.to(x2.dtype).reshape(M, N).contiguous()
+        if need_x:
+            wt = _weight_cast(lib, weight, x2.dtype, True)                   # W^T [K, N]: the data gradient's w
+            dx = _gemm(lib, dy, wt, None, M, K, N)
+        if need_w or need_b:
+            odt = torch.float32 if weight.dtype == torch.float32 else x2.dtype
+            dw = torch.empty(N, K, dtype=odt, device=x2.device)              # (a frozen weight with a trained bias: scratch)
+            db = torch.empty(N, dtype=odt, device=x2.device) if need_b else None
+            dt = DTYPES[x2.dtype]
+            nbytes = lib.bg_linear_wgrad_workspace_bytes(M, N, K, split)
+            ws = workspace(nbytes, x2.device)
+            _lib.check(lib.bg_linear_wgrad(_lib.ptr(dy), N, _lib.ptr(x2), K, _lib.ptr(dw), _lib.ptr(db), M, N, K, dt, DTYPES[odt],
+                                           split, _lib.ptr(ws), nbytes, _lib.stream()), "bg_linear_wgrad")
+            if not need_w:
+                dw = None
+            if db is not None and db.dtype != bias_dtype:
+                db = db.to(bias_dtype)
+    return dx, dw, db
+
+
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, split):
@@ -65,31 +95,9 @@ class _Linear(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dy):
         x2, weight = ctx.saved_tensors
-        lib = _lib.load()
-        N, K = weight.shape
-        M = x2.shape[0]
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.bias_dtype is not None and ctx.needs_input_grad[2]
-        dx = dw = db = None
-        with torch.autocast(device_type="cuda", enabled=False):
-            dy = dy.to(x2.dtype).reshape(M, N).contiguous()
-            if need_x:
-                wt = _weight_cast(lib, weight, x2.dtype, True)                   # W^T [K, N]: the data gradient's w
-                dx = _gemm(lib, dy, wt, None, M, K, N).view(ctx.x_shape)
-            if need_w or need_b:
-                # one launch writes both in ONE dtype: the weight's when that is fp32 (the trainers' masters), otherwise x's
-                odt = torch.float32 if weight.dtype == torch.float32 else x2.dtype
-                dw = torch.empty(N, K, dtype=odt, device=x2.device)              # (a frozen weight with a trained bias: scratch)
-                db = torch.empty(N, dtype=odt, device=x2.device) if need_b else None
-                dt = DTYPES[x2.dtype]
-                nbytes = lib.bg_linear_wgrad_workspace_bytes(M, N, K, ctx.split)
-                ws = workspace(nbytes, x2.device)
-                _lib.check(lib.bg_linear_wgrad(_lib.ptr(dy), N, _lib.ptr(x2), K, _lib.ptr(dw), _lib.ptr(db), M, N, K, dt, DTYPES[odt],
-                                               ctx.split, _lib.ptr(ws), nbytes, _lib.stream()), "bg_linear_wgrad")
-                if not need_w:
-                    dw = None
-                if db is not None and db.dtype != ctx.bias_dtype:
-                    db = db.to(ctx.bias_dtype)
-        return dx, dw, db, None
+        dx, dw, db = linear_backward(x2, weight, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                     ctx.bias_dtype is not None and ctx.needs_input_grad[2], ctx.bias_dtype, ctx.split)
+        return None if dx is None else dx.view(ctx.x_shape), dw, db, None
 
 
 def linear(x, weight, bias=None, split=0):

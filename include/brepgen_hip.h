@@ -327,6 +327,67 @@ int bg_ln_silu_bwd(const void* dh, int h_dtype, const void* x, int x_dtype, cons
 int bg_masked_mse_bwd(const float* pred, const float* target, const uint8_t* row_mask, long long rows, int ld, int col0, int ncols,
                       const float* out3, const float* g, float* dpred, bg_stream_t stream);
 
+/* ---- a VAE ResnetBlock2D's convolution layer in TRAINING (csrc/conv_train.hip): the backward of
+ *     y = conv(act(GroupNorm(x))) + bias          (diffusers ResnetBlock2D.norm1/conv1, norm2/conv2 -- network.py via diffusers)
+ * whose forward is bg_groupnorm_stats, bg_im2col with a 1x1 window (norm + activation + cast -> the 16-bit `a`) and bg_conv_gemm_fwd or
+ * bg_im2col + bg_gemm_bias_act_fwd (see "VAE steps" below).  Activations are channels-last [S, H, W, C] (1-D: H = 1); convolutions are
+ * stride 1 with 'same' zero padding, window kh x kw, both odd and <= 5; H and W are powers of two; 16-bit operands are BG_BF16 | BG_F16.
+ * No atomics, one writer per output element, fixed summation order: two calls give the same bits.  Arguments are checked before any
+ * launch.  The DATA gradient has no entry of its own: it is the 'same' forward convolution of dy (cast to 16 bits by bg_im2col with a
+ * 1x1 window and no norm) with the data-gradient pack of bg_conv_weight_pack, on bg_conv_gemm_fwd or, below that entry's 64-tile
+ * rule, bg_im2col + bg_gemm_bias_act_fwd.  Not covered: stride-2 and up-sampling convolutions, conv_in / conv_out (3 and 6 channels). */
+
+/* dw [N, kh*kw*C] (tap-major / channel-minor: tap = ky*kw + kx, the layout of the forward's packed weight) and db [N] (may be NULL):
+ *     dw[n, tap, c] = sum_{s,y,x} dy[s,y,x,n] * a[s, y + ky - kh/2, x + kx - kw/2, c]      db[n] = sum_{s,y,x} dy[s,y,x,n]
+ * with taps outside the H x W grid of the SAME sample contributing zero.  dy: 16-bit [S*H*W, N], pixel stride ld_dy >= N; a: 16-bit
+ * [S, H, W, C], already normalised and activated, pixel stride ld_a >= C; strides in elements, multiples of 8; bases 16-byte aligned.
+ * out_dtype: BG_F32 or `dtype`.  N % 128 == 0 and C % 128 == 0 (BG_E_SHAPE): a 128-column tile of dw then lies inside one tap, and
+ * the loader's row for output pixel m is the pixel shifted by that tap, zero-filled in registers where it leaves the sample's grid
+ * -- never read from memory, never taken from the neighbouring sample; no im2col matrix is written.  Otherwise bg_linear_wgrad's
+ * kernel and rules with M = S*H*W and K = kh*kw*C: 128 x 128 tiles x slices of whole 32-pixel steps, split = 0 (auto: never an empty slice) or 1 .. 64
+ * (a forced split beyond the row steps leaves trailing slices empty: zero partials), split > 1 through fp32 partials [split][N][K] then [split][N] in the workspace and bg_linear_wgrad's reduce
+ * kernel; S == 0 writes zeros.  With fp32 output row n of dw depends on column n of dy alone; a non-finite dy[m, n] makes dw[n, :]
+ * and db[n] non-finite (a GradScaler's found_inf trips) and leaves the other rows finite. */
+int bg_conv_wgrad(const void* dy, int ld_dy, const void* a, int ld_a, void* dw, void* db, int S, int H, int W, int N, int C, int kh,
+                  int kw, int dtype, int out_dtype, int split, void* workspace, size_t workspace_bytes, bg_stream_t stream);
+/* 0 for split == 1 (or an auto split that resolves to 1), else 4 * split * N * (kh*kw*C + 1) rounded up to 256 bytes; 0 for rejected
+ * arguments. */
+size_t bg_conv_wgrad_workspace_bytes(int S, int H, int W, int N, int C, int kh, int kw, int split);
+/* host-side plan, no device call: the split that 0 resolves to (1 for rejected arguments) */
+int bg_conv_wgrad_split(int S, int H, int W, int N, int C, int kh, int kw);
+
+/* src: an nn.Conv2d / nn.Conv1d weight [N, C, kh, kw] (fp32, or 16-bit of `dtype`) -> either or both of
+ *     fwd   [N, kh*kw*C]   fwd[n, tap, c] = src[n, c, tap]                       the forward's (and bg_conv_wgrad's) layout
+ *     dgrad [C, kh*kw*N]   dgrad[c, kh*kw - 1 - tap, n] = src[n, c, tap]         taps reversed, channels swapped
+ * both 16-bit of `dtype`, round to nearest even: autocast's per-step weight cast.  A 'same' forward convolution of dy [.., N] with
+ * dgrad is the data gradient of the convolution with src.  N % 32 == 0, C % 32 == 0, window odd and <= 5 x 5; dense, 16-byte
+ * aligned.  One launch: 32 x 32 x kh*kw blocks through LDS. */
+int bg_conv_weight_pack(const void* src, int src_dtype, int N, int C, int kh, int kw, void* fwd, void* dgrad, int dtype,
+                        bg_stream_t stream);
+
+/* Workspace of bg_gn_act_bwd: the fp64 partial sums [S][ceil(P / 64)][3][C], the fp64 sums [S][3][C] and the fp32 means [S][G][4], each
+ * rounded up to 256 bytes; 0 for rejected shapes. */
+size_t bg_gn_act_bwd_workspace_bytes(int S, int P, int C, int G);
+/* The backward of a = act(GroupNorm(x)) as bg_im2col applies it (act: bg_vae_act -- none, SiLU, GELU-erf).  da, x, dx fp32 [S, P, C]
+ * dense; stats [S, G, 2] as bg_groupnorm_stats wrote them; gamma, beta fp32 [C]; dskip fp32 [S, P, C] or NULL: the gradient that
+ * arrives over the residual connection, added into dx in the same pass.  With
+ *     xh = (x - mean) * rstd,   v = xh * gamma + beta,   dv = da * act'(v)
+ * pass 1 writes sum_p dv, sum_p dv * xh and sum_p (x - mean) per (sample, channel) over chunks of 64 positions (within a chunk a chain takes every R-th
+ * position, R = max(1, 256 / (C / 4))); the chains of a chunk, then the chunks, are added in index order.  All of it is fp64 from the
+ * first term -- dv and xh are fp32 values, their product is exact in fp64 -- so no fp32 chain exists at all (fp32 chains of 32
+ * positions missed the tests' yardstick at [2, 64, 512]).  From those: dbeta[c] = sum_s sum_p dv and dgamma[c] = sum_s sum_p dv * xh
+ * (the samples in four contiguous quarters, in fp64, rounded once; both NULL = not computed, one NULL is BG_E_ARG) and per (sample,
+ * group) m1 = mean(dv * gamma), m2 = mean(dv * gamma * xh) over P * C / G elements, rounded to fp32.  The third sum gives
+ * delta = mean_group(x - mean), what the fp32 statistics' mean is off by (a few ulp of |mean|; with |mean| = 50 std the largest error of
+ * this backward): the second sum is corrected by - delta * rstd * sum_p dv, and pass 2 forms xh = ((x - mean) - delta) * rstd.  Pass 2
+ * writes every element of
+ *     dx = rstd * fmaf(-xh, m2, fmaf(dv, gamma, -m1)) [+ dskip]       (= rstd * (dv * gamma - m1 - xh * m2), two roundings fewer)
+ * -- with dskip, the bits of the call without it plus one fp32 add.  C % 4 == 0, G divides C, P >= 1, 1 <= S <= 65535 (BG_E_SHAPE);
+ * 16-byte accesses, all bases 16-byte aligned (stats: 8).  Four launches (three without dgamma / dbeta), no host synchronisation. */
+int bg_gn_act_bwd(const float* da, const float* x, const float* stats, const float* gamma, const float* beta, const float* dskip,
+                  float* dx, float* dgamma, float* dbeta, int S, int P, int C, int G, int act, void* workspace, size_t workspace_bytes,
+                  bg_stream_t stream);
+
 /* QKV projection with the LayerNorm fold + self-attention in ONE launch (csrc/qkv_attn.hip): sequences of an even length
  * N <= 64, all B of them equally long; key_pad (may be NULL) as bg_attn_fwd's.  x_hi [B*N, 768] raw 16-bit rows, w_qkv [2304, 768] /
  * bias / colsum as bg_gemm_ex_fwd's fold operands, stats_in [12][B*N][2] the row statistics partials of x; out [B*N, 768] = what
