@@ -1,5 +1,6 @@
-"""What the training ops of the encoder share (attention.py, linear.py, layer.py): the dtype table, the device check, the dropout
-draw state of a module and the normalisation of a dropout key, and four small helpers of the autograd functions and converters.
+"""What the training ops share (attention.py, linear.py, layer.py, mlp.py, conv.py): the dtype table, the device check, the autocast
+rule, the dropout draw state of a module and the normalisation of a dropout key, the weight-gradient output rule, and the small
+helpers of the autograd functions and converters.
 
 Dropout draw ids.  A module that drops (MultiheadSelfAttention, DeviceEncoderLayer) is a `DropoutDraws`: layer i of an encoder of L
 layers gives its training-mode forward number `calls` the draw id  (calls * L + i) mod 2^32,  so no two (layer, training forward)
@@ -20,6 +21,24 @@ HALF = (torch.float16, torch.bfloat16)
 def require_device(t, what):
     if not getattr(t, "is_cuda", False):
         raise _lib.BrepgenHipError(f"{what} runs on the MI355X only (a device tensor is required); there is no CPU fallback")
+
+
+def require_devices(what, x, **named):
+    """`require_device` for x under the name `what` and for every named tensor that is not None under `what (name)`"""
+    require_device(x, what)
+    for name, t in named.items():
+        if t is not None:
+            require_device(t, f"{what} ({name})")
+
+
+def autocast_dtype():
+    """the autocast dtype inside torch.autocast, None outside"""
+    return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+
+
+def default_out_dtype(x):
+    """the default output dtype of an op on x: the autocast dtype inside torch.autocast, x's dtype otherwise"""
+    return autocast_dtype() or x.dtype
 
 
 class DropoutDraws:
@@ -64,6 +83,23 @@ def fp32(param):
 def workspace(nbytes, device):
     """`nbytes` of scratch for one launch (the allocator's alignment covers every kernel's), None for 0"""
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def grad_as(t, dtype):
+    """a parameter gradient (or None) in the parameter's dtype"""
+    return t if t is None or t.dtype == dtype else t.to(dtype)
+
+
+def weight_grad(weight, dt, shape, need_w, need_b, nbytes, launch):
+    """The output rule of a weight-gradient entry (bg_linear_wgrad, bg_conv_wgrad): dw of `shape` and db [shape[0]] come out of ONE
+    launch in one dtype -- fp32 for an fp32 master `weight`, otherwise the operand dtype dt -- with `nbytes` of workspace;
+    launch(dw, db, out dtype code, ws, nbytes) returns the entry's status.  db is allocated only for need_b; a frozen weight with a
+    trained bias gets a scratch dw.  Returns (dw or None, db or None)."""
+    odt = torch.float32 if weight.dtype == torch.float32 else dt
+    dw = torch.empty(shape, dtype=odt, device=weight.device)
+    db = torch.empty(shape[0], dtype=odt, device=weight.device) if need_b else None
+    launch(dw, db, DTYPES[odt], workspace(nbytes, weight.device), nbytes)
+    return (dw if need_w else None), db
 
 
 def adopt(new, old, *names):

@@ -24,11 +24,10 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._train import DTYPES, HALF, adopt, fp32, require_device, workspace
-from .linear import linear, linear_backward
+from ._train import DTYPES, HALF, adopt, autocast_dtype, fp32, grad_as, require_device, weight_grad, workspace
+from .linear import TILE, linear, linear_backward
 
 ACTS = {"none": 0, "silu": 1, "gelu": 2}         # bg_vae_act
-TILE = 128                                        # bg_conv_wgrad: N % 128 == 0 and C % 128 == 0
 _ZERO = {}
 
 
@@ -127,13 +126,10 @@ class _Layer:
             dy16 = _norm_act_cast(lib, dy, S, H, W, N, dt)
         dx = dgamma = dbeta = dw = db = None
         if need_w or need_b:
-            odt = torch.float32 if self.weight.dtype == torch.float32 else dt
-            dwp = torch.empty(N, kh * kw * C, dtype=odt, device=dev)
-            db = torch.empty(N, dtype=odt, device=dev) if need_b else None
-            nbytes = lib.bg_conv_wgrad_workspace_bytes(S, H, W, N, C, kh, kw, 0)
-            ws = workspace(nbytes, dev)
-            _lib.check(lib.bg_conv_wgrad(_lib.ptr(dy16), N, _lib.ptr(self.a), C, _lib.ptr(dwp), _lib.ptr(db), S, H, W, N, C, kh, kw, DTYPES[dt],
-                                         DTYPES[odt], 0, _lib.ptr(ws), nbytes, _lib.stream()), "bg_conv_wgrad")
+            dwp, db = weight_grad(self.weight, dt, (N, kh * kw * C), need_w, need_b, lib.bg_conv_wgrad_workspace_bytes(S, H, W, N, C, kh, kw, 0),
+                                  lambda dwp, db, odt, ws, nbytes: _lib.check(lib.bg_conv_wgrad(
+                                      _lib.ptr(dy16), N, _lib.ptr(self.a), C, _lib.ptr(dwp), _lib.ptr(db), S, H, W, N, C, kh, kw, DTYPES[dt], odt, 0,
+                                      _lib.ptr(ws), nbytes, _lib.stream()), "bg_conv_wgrad"))
             if need_w:                                     # tap-major [N, kh, kw, C] -> the parameter's [N, C, kh, kw] / [N, C, kw]
                 dw = (dwp.view(N, kw, C).permute(0, 2, 1) if self.weight.dim() == 3 else dwp.view(N, kh, kw, C).permute(0, 3, 1, 2)).contiguous()
         if need_x or (need_gn and self.gn):
@@ -152,11 +148,6 @@ class _Layer:
             else:
                 dx = da if dskip is None else da + dskip
         return dx, dgamma, dbeta, dw, db, dy16
-
-
-def _as(t, like):
-    """a parameter gradient in the parameter's dtype"""
-    return t if t is None or t.dtype == like.dtype else t.to(like.dtype)
 
 
 class _GnActConv(torch.autograd.Function):
@@ -180,14 +171,14 @@ class _GnActConv(torch.autograd.Function):
             dy = dy.float().contiguous()
             dx, dgamma, dbeta, dw, db, _ = L.backward(dy.view(-1, L.N), need[0], need[1] or need[2], need[3], bias is not None and need[4])
         dx = None if dx is None or not need[0] else dx.view(L.x.shape)
-        return (dx, _as(dgamma, gamma) if need[1] else None, _as(dbeta, beta) if need[2] else None, _as(dw, weight),
-                _as(db, bias) if bias is not None else None, dy if need[5] else None, None, None, None, None)
+        return (dx, grad_as(dgamma, gamma.dtype) if need[1] else None, grad_as(dbeta, beta.dtype) if need[2] else None,
+                grad_as(dw, weight.dtype), grad_as(db, bias.dtype) if bias is not None else None, dy if need[5] else None, None, None, None, None)
 
 
 def _autocast_dtype(what):
-    if not torch.is_autocast_enabled("cuda"):
+    dt = autocast_dtype()
+    if dt is None:
         raise ValueError(f"{what}: called outside torch.autocast (the trainers run under fp16 / bf16 autocast; an fp32 product is not provided)")
-    dt = torch.get_autocast_dtype("cuda")
     if dt not in HALF:
         raise ValueError(f"{what}: autocast dtype {dt} (fp16 or bf16)")
     return dt
@@ -295,7 +286,7 @@ class _Resnet(torch.autograd.Function):
         grads = [dx.view(S, H, W, C) if need[0] else None, None]
         for g, p, n in ((dg1, g1, 2), (db1, b1, 3), (dw1, w1, 4), (dc1, c1, 5), (dg2, g2, 6), (db2, b2, 7), (dw2, w2, 8), (dc2, c2, 9),
                         (dws, ws, 10), (dcs, cs, 11)):
-            grads.append(_as(g, p) if p is not None and need[n] else None)
+            grads.append(grad_as(g, p.dtype) if p is not None and need[n] else None)
         return (*grads, None, None)
 
 

@@ -123,23 +123,6 @@ __global__ __launch_bounds__(256, 2) void cw_wgrad_kernel(const void* __restrict
     if (with_db) lb_store_db<F16, OUT>(dbacc, lds, db_, (OUT == 0 ? (size_t)slice * N : 0) + n0, tid);
 }
 
-template <bool F16>
-static void cw_launch(hipStream_t s, const void* dy, int ld_dy, const void* a, int ld_a, void* dw, void* db, int M, int N, int C, int kh,
-                      int kw, int lh, int lw, bool out16, int S, float* ws) {
-    const int K = kh * kw * C;
-    const dim3 grid((unsigned)((K / 128) * (N / 128) * S));      // one workgroup per (K tile, N tile, slice)
-    const int slice_rows = lb_slice_rows(M, S);
-    if (S > 1) {
-        hipLaunchKernelGGL((cw_wgrad_kernel<F16, 0>), grid, dim3(256), 0, s, dy, ld_dy, a, ld_a, (void*)ws, (void*)(ws + (size_t)S * N * K), M, N,
-                           C, kh, kw, lh, lw, slice_rows);
-        lb_reduce(s, F16, out16, ws, dw, db, S, N, K);
-    } else if (out16) {
-        hipLaunchKernelGGL((cw_wgrad_kernel<F16, 2>), grid, dim3(256), 0, s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, slice_rows);
-    } else {
-        hipLaunchKernelGGL((cw_wgrad_kernel<F16, 1>), grid, dim3(256), 0, s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, slice_rows);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // weight pack: a workgroup takes a 32 (n) x 32 (c) x kh*kw block of the weight through LDS.  The source block is 32 runs of
 // 32 * kh*kw consecutive elements; both outputs leave in 16-byte pieces (64-byte runs).
@@ -423,39 +406,19 @@ extern "C" size_t bg_conv_wgrad_workspace_bytes(int S, int H, int W, int N, int 
 extern "C" int bg_conv_wgrad(const void* dy, int ld_dy, const void* a, int ld_a, void* dw, void* db, int S, int H, int W, int N, int C,
                              int kh, int kw, int dtype, int out_dtype, int split, void* workspace, size_t workspace_bytes,
                              bg_stream_t stream) {
-    BG_REQUIRE(dtype == BG_BF16 || dtype == BG_F16, BG_E_DTYPE, "bg_conv_wgrad: operand dtype %d (BG_BF16 or BG_F16)", dtype);
-    BG_REQUIRE(out_dtype == BG_F32 || out_dtype == dtype, BG_E_DTYPE, "bg_conv_wgrad: out_dtype %d is neither BG_F32 nor the operand dtype %d",
-               out_dtype, dtype);
+    if (int e = lb_wgrad_dtypes("bg_conv_wgrad", dtype, out_dtype)) return e;
     BG_REQUIRE(S >= 0 && cw_log2(H) >= 0 && cw_log2(W) >= 0 && (long long)S * H * W < (1ll << 31) - 4096, BG_E_SHAPE,
                "bg_conv_wgrad: S = %d samples of an H = %d x W = %d grid (powers of two, fewer than 2^31 pixels)", S, H, W);
     BG_REQUIRE(kh >= 1 && kw >= 1 && kh <= 5 && kw <= 5 && (kh & 1) && (kw & 1), BG_E_SHAPE,
                "bg_conv_wgrad: window %d x %d (odd, each at most 5)", kh, kw);
     BG_REQUIRE(N >= 128 && C >= 128 && N % 128 == 0 && C % 128 == 0 && (long long)N * kh * kw * C < (1ll << 31), BG_E_SHAPE,
                "bg_conv_wgrad: N = %d and C = %d must be multiples of 128", N, C);
-    BG_REQUIRE(split >= 0 && split <= LB_MAX_SPLIT, BG_E_ARG, "bg_conv_wgrad: split = %d outside [0, %d] (0 = auto)", split, LB_MAX_SPLIT);
-    BG_REQUIRE(dw != nullptr, BG_E_ARG, "bg_conv_wgrad: null pointer (dw)");
-    BG_REQUIRE(S == 0 || (dy != nullptr && a != nullptr), BG_E_ARG, "bg_conv_wgrad: null pointer (dy, a)");
-    BG_REQUIRE(ld_dy >= N && ld_a >= C && ld_dy % 8 == 0 && ld_a % 8 == 0, BG_E_ALIGN,
-               "bg_conv_wgrad: pixel strides ld_dy = %d (>= N), ld_a = %d (>= C) must be multiples of 8 elements", ld_dy, ld_a);
-    BG_REQUIRE(aligned(dy, 16) && aligned(a, 16) && aligned(dw, 16) && aligned(db, 16) && aligned(workspace, 16), BG_E_ALIGN,
-               "bg_conv_wgrad: 16-byte alignment of dy / a / dw / db / workspace");
-    hipStream_t s = (hipStream_t)stream;
-    const int K = kh * kw * C, M = S * H * W;
-    const size_t esz = out_dtype == BG_F32 ? 4 : 2;
-    if (M == 0) {
-        hipError_t e = hipMemsetAsync(dw, 0, (size_t)N * K * esz, s);
-        if (e == hipSuccess && db) e = hipMemsetAsync(db, 0, (size_t)N * esz, s);
-        BG_REQUIRE(e == hipSuccess, (int)e, "bg_conv_wgrad: hipMemsetAsync: %s", hipGetErrorString(e));
-        return 0;
-    }
-    const int SP = split == 0 ? lb_auto_split(M, N, K) : split;
-    const size_t need = lb_workspace(N, K, SP);
-    BG_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), BG_E_ARG,
-               "bg_conv_wgrad: workspace of %zu bytes, %zu needed for split = %d", workspace ? workspace_bytes : (size_t)0, need, SP);
-    const int lh = cw_log2(H), lw = cw_log2(W);
-    if (dtype == BG_F16) cw_launch<true>(s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, out_dtype != BG_F32, SP, (float*)workspace);
-    else cw_launch<false>(s, dy, ld_dy, a, ld_a, dw, db, M, N, C, kh, kw, lh, lw, out_dtype != BG_F32, SP, (float*)workspace);
-    return launch_status("conv_wgrad");
+    const int M = S * H * W, lh = cw_log2(H), lw = cw_log2(W);
+    return lb_wgrad_entry("bg_conv_wgrad", "a", "C", "pixel", dy, ld_dy, a, ld_a, C, dw, db, M, N, kh * kw * C, dtype, out_dtype, split, true,
+                          workspace, workspace_bytes, stream, [&](auto F, auto OUT, dim3 grid, void* dw_, void* db_, int slice_rows) {
+                              hipLaunchKernelGGL((cw_wgrad_kernel<decltype(F)::value, decltype(OUT)::value>), grid, dim3(256), 0,
+                                                 (hipStream_t)stream, dy, ld_dy, a, ld_a, dw_, db_, M, N, C, kh, kw, lh, lw, slice_rows);
+                          });
 }
 
 extern "C" int bg_conv_weight_pack(const void* src, int src_dtype, int N, int C, int kh, int kw, void* fwd, void* dgrad, int dtype,

@@ -259,25 +259,6 @@ void lb_reduce(hipStream_t s, bool f16, bool out16, const float* ws, void* dw, v
     });
 }
 
-template <bool F16>
-static void lb_launch(hipStream_t s, const void* dy, int ld_dy, const void* x, int ld_x, void* dw, void* db, int M, int N, int K,
-                      bool out16, int S, float* ws) {
-    const dim3 grid((unsigned)((K / 128) * (N / 128) * S));      // one workgroup per (K tile, N tile, slice): lb_wgrad_kernel's walk
-    const int slice_rows = lb_slice_rows(M, S);
-    const char* walk = getenv("BG_LINEAR_WGRAD_WALK");      // "plain": block order as launched, for the in-process A/B and its bit test
-    const int plain = walk != nullptr && walk[0] == 'p';
-    if (S > 1) {
-        const size_t nk = (size_t)N * K;
-        hipLaunchKernelGGL((lb_wgrad_kernel<F16, 0>), grid, dim3(256), 0, s, dy, ld_dy, x, ld_x, (void*)ws, (void*)(ws + (size_t)S * nk), M, N, K,
-                           slice_rows, plain);
-        lb_reduce(s, F16, out16, ws, dw, db, S, N, K);
-    } else if (out16) {
-        hipLaunchKernelGGL((lb_wgrad_kernel<F16, 2>), grid, dim3(256), 0, s, dy, ld_dy, x, ld_x, dw, db, M, N, K, slice_rows, plain);
-    } else {
-        hipLaunchKernelGGL((lb_wgrad_kernel<F16, 1>), grid, dim3(256), 0, s, dy, ld_dy, x, ld_x, dw, db, M, N, K, slice_rows, plain);
-    }
-}
-
 }  // namespace bg
 
 using namespace bg;
@@ -294,37 +275,17 @@ extern "C" size_t bg_linear_wgrad_workspace_bytes(int M, int N, int K, int split
 
 extern "C" int bg_linear_wgrad(const void* dy, int ld_dy, const void* x, int ld_x, void* dw, void* db, int M, int N, int K, int dtype,
                                int out_dtype, int split, void* workspace, size_t workspace_bytes, bg_stream_t stream) {
-    BG_REQUIRE(dtype == BG_BF16 || dtype == BG_F16, BG_E_DTYPE, "bg_linear_wgrad: operand dtype %d (BG_BF16 or BG_F16)", dtype);
-    BG_REQUIRE(out_dtype == BG_F32 || out_dtype == dtype, BG_E_DTYPE, "bg_linear_wgrad: out_dtype %d is neither BG_F32 nor the operand dtype %d",
-               out_dtype, dtype);
+    if (int e = lb_wgrad_dtypes("bg_linear_wgrad", dtype, out_dtype)) return e;
     BG_REQUIRE(M >= 0, BG_E_SHAPE, "bg_linear_wgrad: M = %d is negative", M);
     BG_REQUIRE(N >= 128 && K >= 128 && N % 128 == 0 && K % 128 == 0 && N / 128 <= 65535, BG_E_SHAPE,
                "bg_linear_wgrad: N = %d and K = %d must be multiples of 128", N, K);
-    BG_REQUIRE(split >= 0 && split <= LB_MAX_SPLIT, BG_E_ARG, "bg_linear_wgrad: split = %d outside [0, %d] (0 = auto)", split, LB_MAX_SPLIT);
-    BG_REQUIRE(dw != nullptr, BG_E_ARG, "bg_linear_wgrad: null pointer (dw)");
-    BG_REQUIRE(M == 0 || (dy != nullptr && x != nullptr), BG_E_ARG, "bg_linear_wgrad: null pointer (dy, x)");
-    BG_REQUIRE(ld_dy >= N && ld_x >= K && ld_dy % 8 == 0 && ld_x % 8 == 0, BG_E_ALIGN,
-               "bg_linear_wgrad: row strides ld_dy = %d (>= N), ld_x = %d (>= K) must be multiples of 8 elements", ld_dy, ld_x);
-    BG_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dw & 15) == 0 && ((uintptr_t)db & 15) == 0 &&
-                   ((uintptr_t)workspace & 15) == 0,
-               BG_E_ALIGN, "bg_linear_wgrad: 16-byte alignment of dy / x / dw / db / workspace");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t esz = out_dtype == BG_F32 ? 4 : 2;
-    if (M == 0) {
-        hipError_t e = hipMemsetAsync(dw, 0, (size_t)N * K * esz, s);
-        if (e == hipSuccess && db) e = hipMemsetAsync(db, 0, (size_t)N * esz, s);
-        BG_REQUIRE(e == hipSuccess, (int)e, "bg_linear_wgrad: hipMemsetAsync: %s", hipGetErrorString(e));
-        return 0;
-    }
-    const int S = split == 0 ? lb_auto_split(M, N, K) : split;
-    BG_REQUIRE(lb_no_empty_slice(M, S), BG_E_ARG,
-               "bg_linear_wgrad: split = %d leaves an empty slice for M = %d (slices are whole steps of %d rows)", S, M, LB_RS);
-    const size_t need = lb_workspace(N, K, S);
-    BG_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), BG_E_ARG,
-               "bg_linear_wgrad: workspace of %zu bytes, %zu needed for split = %d", workspace ? workspace_bytes : (size_t)0, need, S);
-    if (dtype == BG_F16) lb_launch<true>(s, dy, ld_dy, x, ld_x, dw, db, M, N, K, out_dtype != BG_F32, S, (float*)workspace);
-    else lb_launch<false>(s, dy, ld_dy, x, ld_x, dw, db, M, N, K, out_dtype != BG_F32, S, (float*)workspace);
-    return launch_status("linear_wgrad");
+    const char* walk = getenv("BG_LINEAR_WGRAD_WALK");      // "plain": block order as launched, for the in-process A/B and its bit test
+    const int plain = walk != nullptr && walk[0] == 'p';
+    return lb_wgrad_entry("bg_linear_wgrad", "x", "K", "row", dy, ld_dy, x, ld_x, K, dw, db, M, N, K, dtype, out_dtype, split, false, workspace,
+                          workspace_bytes, stream, [&](auto F, auto OUT, dim3 grid, void* dw_, void* db_, int slice_rows) {
+                              hipLaunchKernelGGL((lb_wgrad_kernel<decltype(F)::value, decltype(OUT)::value>), grid, dim3(256), 0,
+                                                 (hipStream_t)stream, dy, ld_dy, x, ld_x, dw_, db_, M, N, K, slice_rows, plain);
+                          });
 }
 
 extern "C" int bg_weight_cast(const void* src, int src_dtype, int R, int C, void* dst, void* dst_t, int dtype, bg_stream_t stream) {
@@ -335,8 +296,7 @@ extern "C" int bg_weight_cast(const void* src, int src_dtype, int R, int C, void
                "bg_weight_cast: R = %d and C = %d must be multiples of 64", R, C);
     BG_REQUIRE(src != nullptr, BG_E_ARG, "bg_weight_cast: null pointer (src)");
     BG_REQUIRE(dst != nullptr || dst_t != nullptr, BG_E_ARG, "bg_weight_cast: null pointer (dst and dst_t: at least one output)");
-    BG_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 && ((uintptr_t)dst_t & 15) == 0, BG_E_ALIGN,
-               "bg_weight_cast: 16-byte alignment of src / dst / dst_t");
+    BG_REQUIRE(aligned(src, 16) && aligned(dst, 16) && aligned(dst_t, 16), BG_E_ALIGN, "bg_weight_cast: 16-byte alignment of src / dst / dst_t");
     const dim3 grid(C / 64, R / 64);
     hipStream_t s = (hipStream_t)stream;
     if (src_dtype != BG_F32) hipLaunchKernelGGL(lb_cast_kernel<0>, grid, dim3(256), 0, s, src, dst, dst_t, R, C);

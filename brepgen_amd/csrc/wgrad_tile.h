@@ -1,5 +1,6 @@
 // What the two weight-gradient kernels share (linear_bwd.hip: lb_wgrad_kernel, conv_train.hip: cw_wgrad_kernel): the row-major
-// LDS image of a 32 x 128 operand piece and its transpose-read fragments, the staged-dY bias sum, and the host-side slice plan.
+// LDS image of a 32 x 128 operand piece and its transpose-read fragments, the staged-dY bias sum, the host-side slice plan, and the
+// checked body of their two entries (lb_wgrad_entry).
 // Both kernels reduce over the ROW index of both operands in steps of LB_RS rows; they differ in where a row of the second
 // operand comes from (a row of X; the pixel a tap shifts to, or zeros).  See linear_bwd.hip for the organisation.  The tile-body
 // helpers below (lb_frag_offsets .. lb_store_db) are lb_wgrad_kernel's body, statement for statement; that kernel keeps its inline
@@ -151,5 +152,57 @@ static inline size_t lb_workspace(int N, int K, int S) {
 // dW [N, K] / db [N] (db may be null) = the S fp32 partials of `ws` ([S][N][K], then [S][N]) added in index order, written in fp32 or
 // (out16) the 16-bit dtype: lb_reduce_kernel (linear_bwd.hip)
 void lb_reduce(hipStream_t s, bool f16, bool out16, const float* ws, void* dw, void* db, int S, int N, int K);
+
+// ---- the checked body of the two entries (bg_linear_wgrad | bg_conv_wgrad).  An entry calls lb_wgrad_dtypes, makes its own shape
+// checks, and hands over M x N times M x K with the words of its messages: `op` names the second operand (x | a), `red` its width
+// (K | C, the least ld_op: min_ld_op), `stride` the strides (row | pixel).  empty_ok: trailing slices may be empty (the conv kernel
+// zero-fills them; bg_linear_wgrad rejects such a split).  launch(F16 constant, OUT constant, grid, dw, db, slice_rows) enqueues the
+// entry's tile kernel: OUT 0 writes fp32 partials to the workspace, which lb_reduce then adds up; 1 / 2 write dW / db themselves ----
+static int lb_wgrad_dtypes(const char* who, int dtype, int out_dtype) {
+    BG_REQUIRE(dtype == BG_BF16 || dtype == BG_F16, BG_E_DTYPE, "%s: operand dtype %d (BG_BF16 or BG_F16)", who, dtype);
+    BG_REQUIRE(out_dtype == BG_F32 || out_dtype == dtype, BG_E_DTYPE, "%s: out_dtype %d is neither BG_F32 nor the operand dtype %d", who,
+               out_dtype, dtype);
+    return 0;
+}
+
+template <typename Launch>
+static int lb_wgrad_entry(const char* who, const char* op, const char* red, const char* stride, const void* dy, int ld_dy, const void* b, int ld_op,
+                          int min_ld_op, void* dw, void* db, int M, int N, int K, int dtype, int out_dtype, int split, bool empty_ok,
+                          void* workspace, size_t workspace_bytes, bg_stream_t stream, Launch&& launch) {
+    BG_REQUIRE(split >= 0 && split <= LB_MAX_SPLIT, BG_E_ARG, "%s: split = %d outside [0, %d] (0 = auto)", who, split, LB_MAX_SPLIT);
+    BG_REQUIRE(dw != nullptr, BG_E_ARG, "%s: null pointer (dw)", who);
+    BG_REQUIRE(M == 0 || (dy != nullptr && b != nullptr), BG_E_ARG, "%s: null pointer (dy, %s)", who, op);
+    BG_REQUIRE(ld_dy >= N && ld_op >= min_ld_op && ld_dy % 8 == 0 && ld_op % 8 == 0, BG_E_ALIGN,
+               "%s: %s strides ld_dy = %d (>= N), ld_%s = %d (>= %s) must be multiples of 8 elements", who, stride, ld_dy, op, ld_op, red);
+    BG_REQUIRE(aligned(dy, 16) && aligned(b, 16) && aligned(dw, 16) && aligned(db, 16) && aligned(workspace, 16), BG_E_ALIGN,
+               "%s: 16-byte alignment of dy / %s / dw / db / workspace", who, op);
+    hipStream_t s = (hipStream_t)stream;
+    const bool out16 = out_dtype != BG_F32;
+    if (M == 0) {
+        const size_t esz = out16 ? 2 : 4;
+        hipError_t e = hipMemsetAsync(dw, 0, (size_t)N * K * esz, s);
+        if (e == hipSuccess && db) e = hipMemsetAsync(db, 0, (size_t)N * esz, s);
+        BG_REQUIRE(e == hipSuccess, (int)e, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+        return 0;
+    }
+    const int S = split == 0 ? lb_auto_split(M, N, K) : split;
+    BG_REQUIRE(empty_ok || lb_no_empty_slice(M, S), BG_E_ARG, "%s: split = %d leaves an empty slice for M = %d (slices are whole steps of %d rows)",
+               who, S, M, LB_RS);
+    const size_t need = lb_workspace(N, K, S);
+    BG_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), BG_E_ARG, "%s: workspace of %zu bytes, %zu needed for split = %d", who,
+               workspace ? workspace_bytes : (size_t)0, need, S);
+    const dim3 grid((unsigned)((K / 128) * (N / 128) * S));      // one workgroup per (K tile, N tile, slice)
+    const int slice_rows = lb_slice_rows(M, S);
+    float* ws = (float*)workspace;
+    auto tile = [&](auto F) {
+        if (S > 1) launch(F, std::integral_constant<int, 0>{}, grid, (void*)ws, (void*)(ws + (size_t)S * N * K), slice_rows);
+        else if (out16) launch(F, std::integral_constant<int, 2>{}, grid, dw, db, slice_rows);
+        else launch(F, std::integral_constant<int, 1>{}, grid, dw, db, slice_rows);
+    };
+    if (dtype == BG_F16) tile(std::true_type{});
+    else tile(std::false_type{});
+    if (S > 1) lb_reduce(s, dtype == BG_F16, out16, ws, dw, db, S, N, K);
+    return launch_status(who + 3);          // the entry's name without "bg_"
+}
 
 }  // namespace bg

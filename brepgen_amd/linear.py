@@ -18,9 +18,9 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._train import DTYPES, HALF, adopt, encoder_layers, fp32, require_device, workspace
+from ._train import DTYPES, HALF, adopt, autocast_dtype, encoder_layers, fp32, grad_as, require_devices, weight_grad
 
-TILE = 128           # bg_linear_wgrad: N % 128 == 0 and K % 128 == 0
+TILE = 128           # bg_linear_wgrad / bg_conv_wgrad: N % 128 == 0 and K (C) % 128 == 0
 
 
 def _weight_cast(lib, w, dtype, transposed):
@@ -59,19 +59,11 @@ def linear_backward(x2, weight, dy, need_x, need_w, need_b, bias_dtype, split=0)
             wt = _weight_cast(lib, weight, x2.dtype, True)                   # W^T [K, N]: the data gradient's w
             dx = _gemm(lib, dy, wt, None, M, K, N)
         if need_w or need_b:
-            odt = torch.float32 if weight.dtype == torch.float32 else x2.dtype
-            dw = torch.empty(N, K, dtype=odt, device=x2.device)              # (a frozen weight with a trained bias: scratch)
-            db = torch.empty(N, dtype=odt, device=x2.device) if need_b else None
-            dt = DTYPES[x2.dtype]
-            nbytes = lib.bg_linear_wgrad_workspace_bytes(M, N, K, split)
-            ws = workspace(nbytes, x2.device)
-            _lib.check(lib.bg_linear_wgrad(_lib.ptr(dy), N, _lib.ptr(x2), K, _lib.ptr(dw), _lib.ptr(db), M, N, K, dt, DTYPES[odt],
-                                           split, _lib.ptr(ws), nbytes, _lib.stream()), "bg_linear_wgrad")
-            if not need_w:
-                dw = None
-            if db is not None and db.dtype != bias_dtype:
-                db = db.to(bias_dtype)
-    return dx, dw, db
+            dw, db = weight_grad(weight, x2.dtype, (N, K), need_w, need_b, lib.bg_linear_wgrad_workspace_bytes(M, N, K, split),
+                                 lambda dw, db, odt, ws, nbytes: _lib.check(lib.bg_linear_wgrad(
+                                     _lib.ptr(dy), N, _lib.ptr(x2), K, _lib.ptr(dw), _lib.ptr(db), M, N, K, DTYPES[x2.dtype], odt, split,
+                                     _lib.ptr(ws), nbytes, _lib.stream()), "bg_linear_wgrad"))
+    return dx, dw, grad_as(db, bias_dtype)
 
 
 class _Linear(torch.autograd.Function):
@@ -119,19 +111,17 @@ def linear(x, weight, bias=None, split=0):
         raise ValueError(f"linear: bias must be [{N}] in fp32 or {x.dtype}, got {tuple(bias.shape)} {bias.dtype}")
     if not 0 <= int(split) <= 64:
         raise ValueError(f"linear: split = {split} outside [0, 64]")
-    require_device(x, "linear")
-    require_device(weight, "linear (weight)")
-    if bias is not None:
-        require_device(bias, "linear (bias)")
+    require_devices("linear", x, weight=weight, bias=bias)
     return _Linear.apply(x, weight, bias, int(split))
 
 
 def linear_autocast(x, weight, bias, what="DeviceLinear"):
     """`linear` after casting a non-16-bit x to the autocast dtype, as autocast would for F.linear; outside autocast such an x raises"""
     if x.dtype not in HALF:
-        if not torch.is_autocast_enabled("cuda"):
+        dt = autocast_dtype()
+        if dt is None:
             raise ValueError(f"{what}: input of dtype {x.dtype} outside torch.autocast (fp16 / bf16 input, or run under autocast)")
-        x = x.to(torch.get_autocast_dtype("cuda"))
+        x = x.to(dt)
     return linear(x, weight, bias)
 
 

@@ -22,8 +22,8 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._train import DTYPES, HALF, fp32, require_device, workspace
-from .layer import D_MODEL
+from ._train import DTYPES, HALF, autocast_dtype, default_out_dtype, fp32, require_device, require_devices, workspace
+from .layer import D_MODEL, row_layer_norm
 from .linear import TILE, linear, linear_autocast
 
 THIN = 48
@@ -116,16 +116,13 @@ def thin_linear_in(x, weight, bias=None, out_dtype=None):
     if x.shape[-1] != weight.shape[1] or x.numel() == 0:
         raise ValueError(f"{what}: x must be [..., {weight.shape[1]}] with at least one row, got {tuple(x.shape)}")
     if out_dtype is None:
-        out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+        out_dtype = default_out_dtype(x)
     if out_dtype not in DTYPES:
         raise ValueError(f"{what}: out_dtype {out_dtype} (fp32, fp16 or bf16)")
     trains = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
     if trains and out_dtype not in HALF:
         raise ValueError(f"{what}: the weight gradient takes a 16-bit dY: run under torch.autocast or pass a 16-bit out_dtype (got {out_dtype})")
-    require_device(x, what)
-    require_device(weight, f"{what} (weight)")
-    if bias is not None:
-        require_device(bias, f"{what} (bias)")
+    require_devices(what, x, weight=weight, bias=bias)
     return _ThinIn.apply(x, weight, bias, out_dtype)
 
 
@@ -170,50 +167,8 @@ def thin_linear_out(a, weight, bias=None):
     _thin_weight(what, weight, bias, 0)
     if a.dim() < 1 or a.shape[-1] != D_MODEL or a.numel() == 0:
         raise ValueError(f"{what}: a must be [..., {D_MODEL}] with at least one row, got {tuple(a.shape)}")
-    require_device(a, what)
-    require_device(weight, f"{what} (weight)")
-    if bias is not None:
-        require_device(bias, f"{what} (bias)")
+    require_devices(what, a, weight=weight, bias=bias)
     return _ThinOut.apply(a, weight, bias)
-
-
-class _LnSilu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps, out_dtype):
-        lib = _lib.load()
-        x2 = x.contiguous()
-        M = x2.numel() // D_MODEL
-        h = torch.empty(x2.shape, dtype=out_dtype, device=x2.device)
-        stats = torch.empty(M, 2, dtype=torch.float32, device=x2.device)
-        _lib.check(lib.bg_ln_silu_train_fwd(_lib.ptr(x2), DTYPES[x2.dtype], _lib.ptr(fp32(weight)), _lib.ptr(fp32(bias)), _lib.ptr(h),
-                                            DTYPES[out_dtype], _lib.ptr(stats), M, eps, _lib.stream()), "bg_ln_silu_train_fwd")
-        ctx.save_for_backward(x2, stats, weight, bias)
-        ctx.out_dtype = out_dtype
-        return h
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dh):
-        x2, stats, weight, bias = ctx.saved_tensors
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        lib = _lib.load()
-        M = x2.numel() // D_MODEL
-        dh = (dh if dh.dtype == ctx.out_dtype else dh.to(ctx.out_dtype)).contiguous()
-        dx = torch.empty_like(x2)
-        dg = db = ws = None
-        nbytes = 0
-        if need_w or need_b:
-            dg = torch.empty(D_MODEL, dtype=torch.float32, device=x2.device)
-            db = torch.empty(D_MODEL, dtype=torch.float32, device=x2.device)
-            nbytes = lib.bg_ln_silu_bwd_workspace_bytes(M)
-            ws = workspace(nbytes, x2.device)
-        _lib.check(lib.bg_ln_silu_bwd(_lib.ptr(dh), DTYPES[dh.dtype], _lib.ptr(x2), DTYPES[x2.dtype], _lib.ptr(stats), _lib.ptr(fp32(weight)),
-                                      _lib.ptr(fp32(bias)), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), M, _lib.ptr(ws), nbytes, _lib.stream()),
-                   "bg_ln_silu_bwd")
-        if dg is not None:
-            dg = dg.to(weight.dtype) if need_w else None
-            db = db.to(bias.dtype) if need_b else None
-        return (dx if need_x else None), dg, db, None, None
 
 
 def ln_silu(x, weight, bias, eps=1e-5, out_dtype=None):
@@ -221,23 +176,7 @@ def ln_silu(x, weight, bias, eps=1e-5, out_dtype=None):
     for dtypes and autocast are layer.layer_norm's: x [..., 768] fp32 / fp16 / bf16; out_dtype default = the autocast dtype inside
     torch.autocast (what the next Linear's cast would make of torch's fp32 result, rounded once), x's dtype otherwise; a 16-bit x
     gives its own dtype or fp32.  Saves x and the rows' (mean, rstd); the backward recomputes LayerNorm(x)."""
-    what = "ln_silu"
-    if x.dtype not in DTYPES:
-        raise ValueError(f"{what}: dtype {x.dtype} (fp32, fp16 or bf16)")
-    if x.dim() < 1 or x.shape[-1] != D_MODEL:
-        raise ValueError(f"{what}: x must be [..., {D_MODEL}], got {tuple(x.shape)}")
-    if tuple(weight.shape) != (D_MODEL,) or tuple(bias.shape) != (D_MODEL,) or not weight.is_floating_point() or not bias.is_floating_point():
-        raise ValueError(f"{what}: weight and bias must be floating [{D_MODEL}], got {tuple(weight.shape)} and {tuple(bias.shape)}")
-    if out_dtype is None:
-        out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
-    if out_dtype not in DTYPES or not (x.dtype == torch.float32 or out_dtype in (torch.float32, x.dtype)):
-        raise ValueError(f"{what}: out_dtype {out_dtype} for x of dtype {x.dtype} (fp32 x: fp32 / fp16 / bf16; 16-bit x: its own dtype or fp32)")
-    if not float(eps) >= 0.0:
-        raise ValueError(f"{what}: eps = {eps} is negative")
-    require_device(x, what)
-    require_device(weight, f"{what} (weight)")
-    require_device(bias, f"{what} (bias)")
-    return _LnSilu.apply(x, weight, bias, float(eps), out_dtype)
+    return row_layer_norm("ln_silu", x, weight, bias, eps, out_dtype, False, True)
 
 
 def _fits(mlp):
@@ -287,7 +226,8 @@ class DeviceMLP(nn.Sequential):
         if l3.out_features > THIN:
             return linear(h, l3.weight, l3.bias)
         y = thin_linear_out(h, l3.weight, l3.bias)
-        return y.to(torch.get_autocast_dtype("cuda")) if torch.is_autocast_enabled("cuda") else y
+        dt = autocast_dtype()
+        return y if dt is None else y.to(dt)
 
 
 def use_device_mlps(model):

@@ -15,6 +15,29 @@ from ._lib import check, ptr, stream
 VAL_STEPS = (10, 50, 100, 200, 500)          # timesteps the reference validates at (trainer.py:394, 587, 781, 1008)
 
 
+def _row_mask(mask, pred):
+    """mask broadcast over pred's rows (EdgePosNet: the [B, S] face mask over [B, S, E, 6] edges), as contiguous uint8, or None.
+    Whether it covers the rows is the caller's check."""
+    if mask is None:
+        return None
+    if mask.dim() < pred.dim() - 1:
+        mask = mask.unsqueeze(-1).expand(pred.shape[:-1])
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
+
+
+def _launch_mse(pred, target, mask, c0, c1):
+    """bg_masked_mse on fp32 pred / target [..., C] and a uint8 row mask (or None): (p, t, out) -- the contiguous operands and
+    out = (mean, row_mean_sum, rows) on the device"""
+    C = pred.shape[-1]
+    p, t = pred.contiguous(), target.contiguous()
+    scratch = torch.empty(1024, device=p.device, dtype=torch.float64)
+    out = torch.empty(3, device=p.device, dtype=torch.float32)
+    check(_lib.load().bg_masked_mse(ptr(p), ptr(t), ptr(mask), p.numel() // C, C, c0, c1 - c0, ptr(scratch), ptr(out), stream()),
+          "bg_masked_mse")
+    return p, t, out
+
+
 def masked_mse(pred, target, mask=None, cols=None):
     """``nn.MSELoss()(pred[~mask], target[~mask])`` and the ``test_val`` reduction, from one deterministic kernel pair.
 
@@ -24,46 +47,18 @@ def masked_mse(pred, target, mask=None, cols=None):
     if not pred.is_cuda:
         raise _lib.BrepgenHipError(f"brepgen_amd runs on the MI355X only (tensor on {pred.device}); no CPU fallback")
     assert pred.shape == target.shape and pred.dtype == torch.float32 and target.dtype == torch.float32
-    C = pred.shape[-1]
-    c0, c1 = cols if cols is not None else (0, C)
-    p, t = pred.contiguous(), target.contiguous()
-    rows = p.numel() // C
-    mk = None
-    if mask is not None:
-        assert mask.shape == pred.shape[:-1]
-        mk = mask.contiguous()
-        mk = mk.view(torch.uint8) if mk.dtype == torch.bool else mk.to(torch.uint8)
-    scratch = torch.empty(1024, device=p.device, dtype=torch.float64)
-    out = torch.empty(3, device=p.device, dtype=torch.float32)
-    check(_lib.load().bg_masked_mse(ptr(p), ptr(t), ptr(mk), rows, C, c0, c1 - c0, ptr(scratch), ptr(out), stream()),
-          "bg_masked_mse")
+    assert mask is None or mask.shape == pred.shape[:-1]
+    c0, c1 = cols if cols is not None else (0, pred.shape[-1])
+    _, _, out = _launch_mse(pred, target, _row_mask(mask, pred), c0, c1)
     return {"mean": out[0], "row_mean_sum": out[1], "rows": out[2]}
-
-
-def _row_mask(mask, pred):
-    """mask broadcast over pred's rows (EdgePosNet: the [B, S] face mask over [B, S, E, 6] edges), as uint8, or None"""
-    if mask is None:
-        return None
-    if mask.dim() < pred.dim() - 1:
-        mask = mask.unsqueeze(-1).expand(pred.shape[:-1])
-    if mask.shape != pred.shape[:-1]:
-        raise ValueError(f"mse_loss: mask {tuple(mask.shape)} does not cover the rows of pred {tuple(pred.shape)}")
-    mask = mask.contiguous()
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
 
 
 class _MseLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, mask, cols):
-        lib = _lib.load()
-        C = pred.shape[-1]
-        p, t = pred.contiguous(), target.contiguous()
-        rows = p.numel() // C
-        scratch = torch.empty(1024, device=p.device, dtype=torch.float64)
-        out = torch.empty(3, device=p.device, dtype=torch.float32)
-        check(lib.bg_masked_mse(ptr(p), ptr(t), ptr(mask), rows, C, cols[0], cols[1] - cols[0], ptr(scratch), ptr(out), stream()), "bg_masked_mse")
+        p, t, out = _launch_mse(pred, target, mask, *cols)
         ctx.save_for_backward(p, t, mask, out)
-        ctx.dims = (rows, C, cols)
+        ctx.dims = (p.numel() // pred.shape[-1], pred.shape[-1], cols)
         return out[0].clone()
 
     @staticmethod
@@ -95,8 +90,11 @@ def mse_loss(pred, target, mask=None, cols=None):
         raise ValueError(f"mse_loss: cols = {cols} outside the {C} columns")
     if not pred.is_cuda or not target.is_cuda:
         raise _lib.BrepgenHipError(f"mse_loss runs on the MI355X only (tensors on {pred.device} / {target.device}); no CPU fallback")
+    mask = _row_mask(mask, pred)
+    if mask is not None and mask.shape != pred.shape[:-1]:
+        raise ValueError(f"mse_loss: mask {tuple(mask.shape)} does not cover the rows of pred {tuple(pred.shape)}")
     with torch.autocast(device_type="cuda", enabled=False):
-        return _MseLoss.apply(pred.float(), target.detach().float(), _row_mask(mask, pred), (c0, c1))
+        return _MseLoss.apply(pred.float(), target.detach().float(), mask, (c0, c1))
 
 
 def use_device_training(model, seed=None):
@@ -130,10 +128,7 @@ def ldm_loss(net, ddpm, x0, timesteps, noise, conditions=(), mask=None, class_la
     x_t = ddpm.add_noise(x0, noise, timesteps)
     args = [x_t, timesteps, *conditions] + ([mask] if mask is not None else []) + [class_label]
     pred = net(*args, is_train) if is_train else net(*args)
-    row_mask = mask
-    if mask is not None and mask.dim() < pred.dim() - 1:           # EdgePosNet: [B,S] face mask over [B,S,E,6] edges
-        row_mask = mask.unsqueeze(-1).expand(pred.shape[:-1])
-    return masked_mse(pred, noise.to(pred.device), row_mask, cols)
+    return masked_mse(pred, noise.to(pred.device), _row_mask(mask, pred), cols)
 
 
 @torch.no_grad()

@@ -5,6 +5,7 @@ import torch
 from brepgen_amd import _lib
 from brepgen_amd import conv as CV
 from tests.hip_ops import DT, NAME, _p, _stream  # noqa: F401
+from tests.linear_ops import draw_pair, wgrad_call, workspace_formula  # noqa: F401
 
 ACT = CV.ACTS
 
@@ -17,23 +18,10 @@ def workspace_bytes(S, H, W, N, C, kh, kw, split):
     return _lib.load().bg_conv_wgrad_workspace_bytes(S, H, W, N, C, kh, kw, split)
 
 
-def workspace_formula(N, K, S):
-    """the header's formula: 0 for S = 1, else the fp32 partials [S][N][K] + [S][N] rounded up to 256 bytes"""
-    return 0 if S <= 1 else (4 * S * N * (K + 1) + 255) // 256 * 256
-
-
 def wgrad(dy, a, S, H, W, N, C, kh, kw, out_dtype=torch.float32, split=0, bias=True, ld_dy=None, ld_a=None, dw=None, db=None):
     """dy / a: tensors (or strided views) holding [S*H*W, N] / [S*H*W, C] pixels; dw / db may be given (guarded views) -> (dw, db)"""
-    dev = dy.device
-    dw = torch.empty(N, kh * kw * C, dtype=out_dtype, device=dev) if dw is None else dw
-    if bias and db is None:
-        db = torch.empty(N, dtype=out_dtype, device=dev)
-    nbytes = workspace_bytes(S, H, W, N, C, kh, kw, split)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
-    _lib.check(_lib.load().bg_conv_wgrad(_p(dy), N if ld_dy is None else ld_dy, _p(a), C if ld_a is None else ld_a, _p(dw),
-                                         _p(db) if bias else None, S, H, W, N, C, kh, kw, DT[dy.dtype], DT[out_dtype], split, _p(ws), nbytes,
-                                         _stream()), "bg_conv_wgrad")
-    return dw, (db if bias else None)
+    return wgrad_call("bg_conv_wgrad", (S, H, W, N, C, kh, kw), dy, a, N if ld_dy is None else ld_dy, C if ld_a is None else ld_a,
+                      (N, kh * kw * C), out_dtype, split, bias, dw, db)
 
 
 def weight_pack(w, dtype, fwd=True, dgrad=True, out_f=None, out_d=None):
@@ -84,7 +72,4 @@ def data_grad(dy, w, dtype):
 
 def draw(S, H, W, N, C, dtype, seed, device="cuda"):
     """standard-normal dy [S, H, W, N] and a [S, H, W, C] rounded to `dtype`"""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    dy = torch.randn(S, H, W, N, generator=g).to(dtype).to(device)
-    a = torch.randn(S, H, W, C, generator=g).to(dtype).to(device)
-    return dy, a
+    return draw_pair((S, H, W), N, C, dtype, seed, device)

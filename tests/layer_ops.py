@@ -30,30 +30,32 @@ def workspace_bytes(M):
     return _lib.load().bg_ln_bwd_workspace_bytes(M)
 
 
-def ln_fwd(x, gamma, beta, y_dtype, eps=1e-5, y=None, stats=None):
-    """x [M, 768] -> (y [M, 768] in y_dtype, stats fp32 [M, 2]); y / stats may be given (guarded views)"""
+def ln_fwd(x, gamma, beta, y_dtype, eps=1e-5, y=None, stats=None, entry="bg_ln_train_fwd"):
+    """x [M, 768] -> (y [M, 768] in y_dtype, stats fp32 [M, 2]); y / stats may be given (guarded views).  entry: bg_ln_train_fwd or
+    mlp_train.hip's bg_ln_silu_train_fwd (tests/mlp_ops.py)"""
     M = x.shape[0]
     y = torch.empty(M, C_LN, dtype=y_dtype, device=x.device) if y is None else y
     stats = torch.empty(M, 2, dtype=torch.float32, device=x.device) if stats is None else stats
-    _lib.check(_lib.load().bg_ln_train_fwd(_p(x), DT[x.dtype], _p(gamma), _p(beta), _p(y), DT[y.dtype], _p(stats), M, eps, _stream()),
-               "bg_ln_train_fwd")
+    _lib.check(getattr(_lib.load(), entry)(_p(x), DT[x.dtype], _p(gamma), _p(beta), _p(y), DT[y.dtype], _p(stats), M, eps, _stream()), entry)
     return y, stats
 
 
-def ln_bwd(dy, x, stats, gamma, dskip=None, grads=True, dx=None, dgamma=None, dbeta=None, ws=None):
-    """-> (dx, dgamma, dbeta); grads=False: dgamma / dbeta NULL, no workspace.  Outputs and workspace may be given (guarded views)."""
+def ln_bwd(dy, x, stats, gamma, dskip=None, grads=True, dx=None, dgamma=None, dbeta=None, ws=None, entry="bg_ln_bwd"):
+    """-> (dx, dgamma, dbeta); grads=False: dgamma / dbeta NULL, no workspace.  Outputs and workspace may be given (guarded views).
+    entry: bg_ln_bwd, or bg_ln_silu_bwd (tests/mlp_ops.py), which takes beta where bg_ln_bwd takes dskip"""
+    lib = _lib.load()
     M, dev = x.shape[0], x.device
     dx = torch.empty(M, C_LN, dtype=x.dtype, device=dev) if dx is None else dx
     nbytes = 0
     if grads:
         dgamma = torch.empty(C_LN, dtype=torch.float32, device=dev) if dgamma is None else dgamma
         dbeta = torch.empty(C_LN, dtype=torch.float32, device=dev) if dbeta is None else dbeta
-        nbytes = workspace_bytes(M)
+        nbytes = getattr(lib, entry + "_workspace_bytes")(M)
         if ws is None and nbytes:
             ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().bg_ln_bwd(_p(dy), DT[dy.dtype], _p(x), DT[x.dtype], _p(stats), _p(gamma), _p(dskip), _p(dx),
-                                     _p(dgamma) if grads else None, _p(dbeta) if grads else None, M, _p(ws) if grads else None, nbytes,
-                                     _stream()), "bg_ln_bwd")
+    _lib.check(getattr(lib, entry)(_p(dy), DT[dy.dtype], _p(x), DT[x.dtype], _p(stats), _p(gamma), _p(dskip), _p(dx),
+                                   _p(dgamma) if grads else None, _p(dbeta) if grads else None, M, _p(ws) if grads else None, nbytes,
+                                   _stream()), entry)
     return dx, (dgamma if grads else None), (dbeta if grads else None)
 
 

@@ -30,20 +30,25 @@ def slices(M, S):
     return [(s * rows, min(M, (s + 1) * rows)) for s in range(S)]
 
 
-def wgrad(dy, x, M, N, K, out_dtype=torch.float32, split=0, bias=True, ld_dy=None, ld_x=None, dw=None, db=None, ws=None):
-    """dy / x: tensors (or strided views) holding [M, N] / [M, K] rows; dw / db / ws may be given (guarded views).  -> (dw, db)"""
-    dev = dy.device
-    dw = torch.empty(N, K, dtype=out_dtype, device=dev) if dw is None else dw
+def wgrad_call(entry, lead, dy, b, ld_dy, ld_b, shape, out_dtype, split, bias, dw, db, ws=None):
+    """The weight-gradient entry `entry` (bg_linear_wgrad, lead = (M, N, K) | bg_conv_wgrad, lead = (S, H, W, N, C, kh, kw)) on dy and
+    its second operand b with their strides; dw (of `shape`) / db / ws may be given (guarded views).  -> (dw, db)"""
+    lib, dev = _lib.load(), dy.device
+    dw = torch.empty(shape, dtype=out_dtype, device=dev) if dw is None else dw
     if bias and db is None:
-        db = torch.empty(N, dtype=out_dtype, device=dev)
-    S = split if split else auto_split(M, N, K)
-    nbytes = workspace_bytes(M, N, K, S)
+        db = torch.empty(shape[0], dtype=out_dtype, device=dev)
+    nbytes = getattr(lib, entry + "_workspace_bytes")(*lead, split)
     if ws is None and nbytes:
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().bg_linear_wgrad(_p(dy), N if ld_dy is None else ld_dy, _p(x), K if ld_x is None else ld_x, _p(dw),
-                                           _p(db) if bias else None, M, N, K, DT[dy.dtype], DT[out_dtype], split, _p(ws), nbytes,
-                                           _stream()), "bg_linear_wgrad")
+    _lib.check(getattr(lib, entry)(_p(dy), ld_dy, _p(b), ld_b, _p(dw), _p(db) if bias else None, *lead, DT[dy.dtype], DT[out_dtype], split,
+                                   _p(ws), nbytes, _stream()), entry)
     return dw, (db if bias else None)
+
+
+def wgrad(dy, x, M, N, K, out_dtype=torch.float32, split=0, bias=True, ld_dy=None, ld_x=None, dw=None, db=None, ws=None):
+    """dy / x: tensors (or strided views) holding [M, N] / [M, K] rows; dw / db / ws may be given (guarded views).  -> (dw, db)"""
+    return wgrad_call("bg_linear_wgrad", (M, N, K), dy, x, N if ld_dy is None else ld_dy, K if ld_x is None else ld_x, (N, K), out_dtype, split,
+                      bias, dw, db, ws)
 
 
 def weight_cast(src, dtype, dst=True, dst_t=True, out=None, out_t=None):
@@ -57,12 +62,17 @@ def weight_cast(src, dtype, dst=True, dst_t=True, out=None, out_t=None):
     return out, out_t
 
 
+def draw_pair(lead, N, K, dtype, seed, device="cuda"):
+    """standard-normal dy [*lead, N] and second operand [*lead, K] rounded to `dtype`"""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    dy = torch.randn(*lead, N, generator=g).to(dtype).to(device)
+    b = torch.randn(*lead, K, generator=g).to(dtype).to(device)
+    return dy, b
+
+
 def draw(M, N, K, dtype, seed, device="cuda"):
     """standard-normal dy [M, N], x [M, K] rounded to `dtype`"""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    dy = torch.randn(M, N, generator=g).to(dtype).to(device)
-    x = torch.randn(M, K, generator=g).to(dtype).to(device)
-    return dy, x
+    return draw_pair((M,), N, K, dtype, seed, device)
 
 
 def reference(dy, x):

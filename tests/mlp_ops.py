@@ -5,6 +5,7 @@ import torch
 
 from brepgen_amd import _lib
 from tests.hip_ops import DT, NAME, _p, _stream  # noqa: F401
+from tests.layer_ops import ln_bwd, ln_fwd
 from tests.layer_ops import workspace_bytes as ln_workspace_bytes
 
 C = 768
@@ -65,29 +66,12 @@ def thin_wgrad(t, u, transposed=False, colsum_of=0, g=None, colsum=None, ws=None
 
 
 def ln_silu_fwd(x, gamma, beta, h_dtype, eps=1e-5, h=None, stats=None):
-    M = x.shape[0]
-    h = torch.empty(M, C, dtype=h_dtype, device=x.device) if h is None else h
-    stats = torch.empty(M, 2, dtype=torch.float32, device=x.device) if stats is None else stats
-    _lib.check(_lib.load().bg_ln_silu_train_fwd(_p(x), DT[x.dtype], _p(gamma), _p(beta), _p(h), DT[h.dtype], _p(stats), M, eps, _stream()),
-               "bg_ln_silu_train_fwd")
-    return h, stats
+    return ln_fwd(x, gamma, beta, h_dtype, eps, h, stats, entry="bg_ln_silu_train_fwd")
 
 
 def ln_silu_bwd(dh, x, stats, gamma, beta, grads=True, dx=None, dgamma=None, dbeta=None, ws=None):
-    M, dev = x.shape[0], x.device
-    dx = torch.empty(M, C, dtype=x.dtype, device=dev) if dx is None else dx
-    nbytes = 0
-    if grads:
-        dgamma = torch.empty(C, dtype=torch.float32, device=dev) if dgamma is None else dgamma
-        dbeta = torch.empty(C, dtype=torch.float32, device=dev) if dbeta is None else dbeta
-        nbytes = _lib.load().bg_ln_silu_bwd_workspace_bytes(M)
-        assert nbytes == ln_workspace_bytes(M)
-        if ws is None and nbytes:
-            ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().bg_ln_silu_bwd(_p(dh), DT[dh.dtype], _p(x), DT[x.dtype], _p(stats), _p(gamma), _p(beta), _p(dx),
-                                          _p(dgamma) if grads else None, _p(dbeta) if grads else None, M, _p(ws) if grads else None, nbytes,
-                                          _stream()), "bg_ln_silu_bwd")
-    return dx, (dgamma if grads else None), (dbeta if grads else None)
+    assert _lib.load().bg_ln_silu_bwd_workspace_bytes(x.shape[0]) == ln_workspace_bytes(x.shape[0])
+    return ln_bwd(dh, x, stats, gamma, beta, grads, dx, dgamma, dbeta, ws, entry="bg_ln_silu_bwd")
 
 
 def masked_mse(pred, target, mask, cols):

@@ -189,13 +189,10 @@ def test_p256_kernels_do_not_spill():
     import re
     import subprocess
     from brepgen_amd import build as b
+    from tests.train_cpu import resource_usage
     src = os.path.join(b.CSRC, "gemm_p256.hip")
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    assert len(names) == len(scratch) and len(names) >= 8              # {bf16, fp16} x {plain, fold, split, split + stats}
+    names, scratch, _, _ = resource_usage("gemm_p256.hip")
+    assert len(names) >= 8                                             # {bf16, fp16} x {plain, fold, split, split + stats}
     for n, sc in zip(names, scratch):
         if "gemm16_p256_kernel" not in n:
             continue
@@ -225,14 +222,8 @@ def test_hand_scheduled_kernels_do_not_spill(src):
     csrc/qkv_attn.hip keeps 96 accumulators + 80 fragment registers + the fold temporaries live in its K loop; a spill would put
     scratch traffic (and hipcc's vmcnt(0) after every reload) into K-steps whose waits are placed by hand; csrc/ffn_fused.hip streams
     its weights into registers several k-slices ahead of their use (a reload's vmcnt(0) would wait for all of them)."""
-    import re
-    import subprocess
-    from brepgen_amd import build as b
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(b.CSRC, src),
-                        "-o", os.devnull], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
+    from tests.train_cpu import resource_usage
+    _, scratch, spills, _ = resource_usage(src)
     assert len(scratch) >= 2 and all(v == 0 for v in scratch) and all(v == 0 for v in spills), (scratch, spills)
 
 
@@ -433,3 +424,26 @@ def test_shared_device_steps_are_defined_once():
     with_rescale = sorted(f for f, t in squeezed.items() if "__expf(m_run-m_use)" in t)
     assert with_rescale == ["attn.hip", "attn_train.hip", "qkv_attn.hip"], with_rescale
     assert all(squeezed[f].count("__expf(m_run-m_use)") == 1 for f in with_rescale)
+
+
+def test_shared_training_host_steps_are_written_once():
+    """The training ops share ONE copy of the autocast rule (brepgen_amd/_train.py) and the CPU tests ONE run of the compiler's
+    resource report (tests/train_cpu.py).  A tripwire against pasting either back: the next training piece starts as a copy of one
+    of these files."""
+    from tests import train_cpu
+    pkg = os.path.dirname(bga.__file__)
+    calls = re.compile(r"\b(?:is_autocast_enabled|get_autocast_dtype)\b")
+    with_calls = []
+    for f in ("_train.py", "attention.py", "linear.py", "layer.py", "mlp.py", "conv.py", "training.py"):
+        with open(os.path.join(pkg, f)) as fh:
+            if calls.search(fh.read()):
+                with_calls.append(f)
+    assert with_calls == ["_train.py"], with_calls
+    here = os.path.dirname(os.path.abspath(__file__))
+    with_report = []
+    for f in sorted(os.listdir(here)):
+        if f.endswith(".py"):
+            with open(os.path.join(here, f)) as fh:
+                if train_cpu.RESOURCE_FLAG[1:] in fh.read():
+                    with_report.append(f)
+    assert with_report == ["train_cpu.py"], with_report

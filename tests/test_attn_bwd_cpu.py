@@ -8,7 +8,6 @@ tests/attn_train_ops.py torch_attention) and differentiated by torch's autograd.
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,8 +19,8 @@ import brepgen_amd as bga
 from brepgen_amd import _lib, attention
 from tests import attn_bwd_restate as R
 from tests import attn_train_ops as ops
+from tests.train_cpu import BF, FAKE, ROOT, assert_exported, resource_usage
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("bg_attn_train_fwd", "bg_attn_bwd_workspace_bytes", "bg_attn_bwd", "bg_attn_dropout_mask")
 
 
@@ -151,8 +150,7 @@ def test_unsupported_calls_and_cpu_tensors_raise():
 
 def test_argument_errors_are_negative_and_explained():
     lib = _lib.load()
-    f = 0x10000                                      # aligned, never dereferenced: validation fails before any launch
-    BF = _lib.BG_BF16
+    f = FAKE                                         # aligned, never dereferenced: validation fails before any launch
 
     def fwd(qkv=f, out=f, lse=f, B=2, N=8, dt=BF, scale=0.125, p=0.0, first=0):
         return lib.bg_attn_train_fwd(qkv, None, out, lse, B, N, dt, scale, p, 1, 0, first, None)
@@ -201,20 +199,13 @@ def test_header_prototypes_match_the_binding():
         res, want = _lib._SIGNATURES[name]
         assert args == want, (name, args, want)
         assert res is (C.c_int if m.group(1) == "int" else C.c_size_t)
-        assert name in _lib.EXPORTS and getattr(lib, name).argtypes == want
-    assert lib.bg_abi_version() == 7
+        assert getattr(lib, name).argtypes == want
+    assert_exported(NEW)
 
 
 def test_training_attention_kernels_use_no_scratch():
     """Every kernel of csrc/attn_train.hip: no scratch memory and no spilled VGPR (the backward kernels keep up to 64 accumulators, 32
     score registers and 32 operand registers live; a spill would put scratch traffic into the tile loop)."""
-    from brepgen_amd import build as b
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(b.CSRC, "attn_train.hip"),
-                        "-o", os.devnull], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    # 4 forward + 8 general + 4 short backward 16-bit, 2 + 4 fp32, the mask kernel
-    assert len(names) == len(scratch) == len(spills) == 23, names
-    assert all(v == 0 for v in scratch) and all(v == 0 for v in spills), list(zip(names, scratch, spills))
+    names, scratch, spills, _ = resource_usage("attn_train.hip")
+    assert len(names) == 23, names                   # 4 forward + 8 general + 4 short backward 16-bit, 2 + 4 fp32, the mask kernel
+    assert all(v == 0 for v in scratch + spills), list(zip(names, scratch, spills))

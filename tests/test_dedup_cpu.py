@@ -5,7 +5,6 @@ import ctypes as C
 import hashlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -170,13 +169,8 @@ def test_the_product_does_not_import_the_oracle():
 def test_hash_kernels_use_no_scratch():
     """One lane per item keeps 8 state words, the 16-word rolling schedule and the next slab (32 floats) in registers; a spill would
     put scratch traffic into every round.  Read from the compiler's resource report, as test_abi_cpu.py does for the GEMMs."""
-    from brepgen_amd import build as b
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(b.CSRC, "hash_dedup.hip"),
-                        "-o", os.devnull], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    assert len(names) == len(scratch) == len(spills) == 5, names      # points (16-byte and 4-byte loads), group keys, claim, keep
+    from tests.train_cpu import resource_usage
+    names, scratch, spills, _ = resource_usage("hash_dedup.hip")
+    assert len(names) == 5, names      # points (16-byte and 4-byte loads), group keys, claim, keep
     assert sum("points_sha256_kernel" in n for n in names) == 2
     assert all(v == 0 for v in scratch) and all(v == 0 for v in spills), list(zip(names, scratch, spills))

@@ -8,8 +8,6 @@ library agree."""
 import ctypes as C
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,21 +20,15 @@ from brepgen_amd import _lib
 from brepgen_amd import layer as L
 from tests import layer_ops as ops
 from tests import layer_restate as R
+from tests.train_cpu import BF, F16, F32, FAKE, ROOT, assert_exported, resource_usage, vp
+from tests.train_cpu import explained as _explained
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("bg_ln_train_fwd", "bg_ln_bwd_workspace_bytes", "bg_ln_bwd", "bg_dropout_add_fwd", "bg_dropout_bwd", "bg_relu_dropout_fwd",
        "bg_relu_dropout_bwd", "bg_dropout_mask")
-FAKE = 0x10000          # a 16-byte aligned address nobody dereferences: every check below fails before anything touches the device
-F32, F16, BF = _lib.BG_F32, _lib.BG_F16, _lib.BG_BF16
-vp = C.c_void_p
 
 
 def test_entries_are_exported_with_the_declared_argtypes():
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "brepgen_hip.h")).read()
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(lib, n)
-        assert re.search(r"\b%s\s*\(" % n, re.sub(r"/\*.*?\*/", "", header, flags=re.S)), n
+    assert_exported(NEW)
     i, z, d, f, u64, u32, ll = C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_ulonglong, C.c_uint, C.c_longlong
     key = [d, u64, u32, i, ll]
     assert _lib._SIGNATURES["bg_ln_train_fwd"] == (i, [vp, i, vp, vp, vp, i, vp, i, f, vp])
@@ -47,14 +39,7 @@ def test_entries_are_exported_with_the_declared_argtypes():
     assert _lib._SIGNATURES["bg_relu_dropout_fwd"] == (i, [vp, vp, i, i, i, i] + key + [vp])
     assert _lib._SIGNATURES["bg_relu_dropout_bwd"] == (i, [vp, vp, vp, i, i, i, d, vp])
     assert _lib._SIGNATURES["bg_dropout_mask"] == (i, [vp, i, i, i] + key + [vp])
-    assert int(re.search(r"#define BG_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == lib.bg_abi_version() == 7
     assert "0xD409" in open(os.path.join(ROOT, "brepgen_amd", "csrc", "philox.h")).read().split("#pragma once")[0]      # the tag list
-
-
-def _explained(rc, code, word):
-    msg = _lib.load().bg_last_error()
-    assert rc == code and rc < 0, (rc, msg)
-    assert word in msg, msg
 
 
 def _ln_fwd(x=FAKE, xd=F32, g=FAKE, b=FAKE, y=FAKE, yd=BF, stats=FAKE, M=5, eps=1e-5):
@@ -305,17 +290,8 @@ def test_dropout_draw_state_of_the_attention_module_and_the_layer():
 
 def test_layer_train_kernels_use_no_scratch_and_do_not_spill():
     """the check tests/test_abi_cpu.py::test_hand_scheduled_kernels_do_not_spill makes for its files"""
-    from brepgen_amd import build as b
-    assert "layer_train.hip" in b.SOURCES
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(b.CSRC, "layer_train.hip"),
-                        "-o", os.devnull], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    sspills = [int(v) for v in re.findall(r"SGPRs Spill: (\d+)", r.stderr)]
-    # 7 LayerNorm forwards, 14 backwards, the reduction, 8 + 8 dropout add / backward, 4 + 2 ReLU-dropout, the mask
-    assert len(names) == len(scratch) == len(spills) == len(sspills) == 45, names
+    names, scratch, spills, sspills = resource_usage("layer_train.hip")
+    assert len(names) == 45, names       # 7 LayerNorm forwards, 14 backwards, the reduction, 8 + 8 dropout add / backward, 4 + 2 ReLU-dropout, the mask
     assert all(v == 0 for v in scratch + spills + sspills), list(zip(names, scratch, spills, sspills))
 
 

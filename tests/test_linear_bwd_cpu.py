@@ -5,9 +5,6 @@ The ABI number: the entries are ADDED ones, and the suite's existing files pin `
 (tests/test_optim_cpu.py, test_dedup_cpu.py, test_dataset_cpu.py, test_metrics_cpu.py, test_vae_full_cpu.py, test_attn_bwd_cpu.py), so
 the number stays; what is asserted here is that header, binding and library agree."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 import torch
@@ -17,26 +14,18 @@ import brepgen_amd as bga
 from brepgen_amd import _lib
 from brepgen_amd import linear as L
 from tests import linear_ops as ops
+from tests.train_cpu import BF, F32, FAKE, assert_exported, explained, resource_usage, vp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("bg_linear_wgrad", "bg_linear_wgrad_workspace_bytes", "bg_linear_wgrad_split", "bg_weight_cast")
-FAKE = 0x10000          # a 16-byte aligned address nobody dereferences: every check below fails before anything touches the device
-BF, F32 = _lib.BG_BF16, _lib.BG_F32
-vp = C.c_void_p
 
 
 def test_entries_are_exported_with_the_declared_argtypes():
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "brepgen_hip.h")).read()
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(lib, n)
-        assert re.search(r"\b%s\s*\(" % n, re.sub(r"/\*.*?\*/", "", header, flags=re.S)), n
+    assert_exported(NEW)
     i, z = C.c_int, C.c_size_t
     assert _lib._SIGNATURES["bg_linear_wgrad"] == (i, [vp, i, vp, i, vp, vp, i, i, i, i, i, i, vp, z, vp])
     assert _lib._SIGNATURES["bg_linear_wgrad_workspace_bytes"] == (z, [i, i, i, i])
     assert _lib._SIGNATURES["bg_linear_wgrad_split"] == (i, [i, i, i])
     assert _lib._SIGNATURES["bg_weight_cast"] == (i, [vp, i, i, i, vp, vp, i, vp])
-    assert int(re.search(r"#define BG_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == lib.bg_abi_version()
 
 
 def _wgrad(dy=FAKE, ld_dy=128, x=FAKE, ld_x=128, dw=FAKE, db=FAKE, M=200, N=128, K=128, dtype=BF, out_dtype=F32, split=1, ws=None, ws_bytes=0):
@@ -63,9 +52,7 @@ def _wgrad(dy=FAKE, ld_dy=128, x=FAKE, ld_x=128, dw=FAKE, db=FAKE, M=200, N=128,
     (dict(x=None), _lib.BG_E_ARG, b"null"),
 ])
 def test_wgrad_argument_errors_are_negative_and_explained(kw, code, word):
-    rc = _wgrad(**kw)
-    assert rc == code and rc < 0, (rc, _lib.load().bg_last_error())
-    assert word in _lib.load().bg_last_error(), _lib.load().bg_last_error()
+    explained(_wgrad(**kw), code, word)
 
 
 @pytest.mark.parametrize("args, code, word", [
@@ -79,9 +66,7 @@ def test_wgrad_argument_errors_are_negative_and_explained(kw, code, word):
     ((FAKE, F32, 64, 64, FAKE, None, F32), _lib.BG_E_DTYPE, b"target dtype"),
 ])
 def test_weight_cast_argument_errors_are_negative_and_explained(args, code, word):
-    rc = _lib.load().bg_weight_cast(*args, None)
-    assert rc == code and rc < 0, (rc, _lib.load().bg_last_error())
-    assert word in _lib.load().bg_last_error(), _lib.load().bg_last_error()
+    explained(_lib.load().bg_weight_cast(*args, None), code, word)
 
 
 M_GRID = (1, 31, 64, 65, 1000, 15360, 25600, 96000)
@@ -167,13 +152,6 @@ def test_use_device_linear_keeps_parameter_identity_and_state_dict_keys(with_att
 
 def test_linear_bwd_kernels_do_not_spill():
     """the check tests/test_abi_cpu.py::test_hand_scheduled_kernels_do_not_spill makes for its files"""
-    from brepgen_amd import build as b
-    assert "linear_bwd.hip" in b.SOURCES
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(b.CSRC, "linear_bwd.hip"),
-                        "-o", os.devnull], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    assert len(names) == len(scratch) == len(spills) >= 13                    # 6 tile kernels, 4 reductions, 3 casts
-    assert all(v == 0 for v in scratch) and all(v == 0 for v in spills), list(zip(names, scratch, spills))
+    names, scratch, spills, sspills = resource_usage("linear_bwd.hip")
+    assert len(names) >= 13                                                   # 6 tile kernels, 4 reductions, 3 casts
+    assert all(v == 0 for v in scratch + spills + sspills), list(zip(names, scratch, spills, sspills))

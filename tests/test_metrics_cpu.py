@@ -163,14 +163,9 @@ def test_chamfer_kernel_keeps_its_instruction_mix_and_does_not_spill():
     fuses the row-minimum and the column-partial chains of fminf pairwise).  Pin that in the ISA: per unrolled 8 x 4 block 16 + 16
     v_min3_f32 in the one-pass loop and 16 in each of the two rows-only loops, no two-operand float minimum, no scratch."""
     import re
-    from brepgen_amd import build as b
-    src = os.path.join(b.CSRC, "metrics.hip")
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-S", "--cuda-device-only", "-c", src, "-o", "-"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    body = re.search(r"^_ZN2bg23chamfer_pairwise_kernel\w*:.*?^\.Lfunc_end\d+:", r.stdout, flags=re.S | re.M).group(0)
+    from tests.train_cpu import resource_usage
+    _, scratch, spills, _, asm = resource_usage("metrics.hip", asm=True)
+    body = re.search(r"^_ZN2bg23chamfer_pairwise_kernel\w*:.*?^\.Lfunc_end\d+:", asm, flags=re.S | re.M).group(0)
     assert len(re.findall(r"\bv_min3_f32\b", body)) == 64 and not re.findall(r"\bv_min_f32", body)
     assert len(re.findall(r"\bv_sub_f32", body)) == 3 * 96 and len(re.findall(r"\bds_min_u32\b", body)) == 1
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
     assert len(scratch) == 2 and not any(scratch) and not any(spills), (scratch, spills)

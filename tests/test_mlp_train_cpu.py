@@ -3,9 +3,7 @@ argument validation, the module swap on the reference-keyed denoisers, the compi
 tests compare against (tests/mlp_restate.py) held against torch's fp64 autograd of the same Sequential and of
 mse_loss(pred[~mask], target[~mask]).  No kernel is launched."""
 import ctypes as C
-import os
 import re
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -19,21 +17,15 @@ from brepgen_amd import _lib, layer, linear, mlp, training
 from oracle.ref_formulation import RefDenoiser
 from tests import mlp_ops as ops
 from tests import mlp_restate as R
+from tests.train_cpu import BF, F16, F32, FAKE, assert_exported, resource_usage, vp
+from tests.train_cpu import explained as _explained
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("bg_thin_expand", "bg_thin_contract", "bg_thin_wgrad_workspace_bytes", "bg_thin_wgrad", "bg_ln_silu_train_fwd",
        "bg_ln_silu_bwd_workspace_bytes", "bg_ln_silu_bwd", "bg_masked_mse_bwd")
-FAKE = 0x10000          # a 16-byte aligned address nobody dereferences: every check below fails before anything touches the device
-F32, F16, BF = _lib.BG_F32, _lib.BG_F16, _lib.BG_BF16
-vp = C.c_void_p
 
 
 def test_entries_are_exported_with_the_declared_argtypes():
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "brepgen_hip.h")).read()
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(lib, n)
-        assert re.search(r"\b%s\s*\(" % n, re.sub(r"/\*.*?\*/", "", header, flags=re.S)), n
+    assert_exported(NEW)
     i, z, f, ll = C.c_int, C.c_size_t, C.c_float, C.c_longlong
     assert _lib._SIGNATURES["bg_thin_expand"] == (i, [vp, i, i, vp, i, vp, vp, i, i, i, vp])
     assert _lib._SIGNATURES["bg_thin_contract"] == (i, [vp, i, vp, vp, vp, i, i, vp])
@@ -43,13 +35,6 @@ def test_entries_are_exported_with_the_declared_argtypes():
     assert _lib._SIGNATURES["bg_ln_silu_bwd_workspace_bytes"] == (z, [i])
     assert _lib._SIGNATURES["bg_ln_silu_bwd"] == (i, [vp, i, vp, i, vp, vp, vp, vp, vp, vp, i, vp, z, vp])
     assert _lib._SIGNATURES["bg_masked_mse_bwd"] == (i, [vp, vp, vp, ll, i, i, i, vp, vp, vp, vp])
-    assert int(re.search(r"#define BG_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == lib.bg_abi_version() == 7
-
-
-def _explained(rc, code, word):
-    msg = _lib.load().bg_last_error()
-    assert rc == code and rc < 0, (rc, msg)
-    assert word in msg, msg
 
 
 def _expand(x=FAKE, xd=F32, ldx=18, w=FAKE, km=0, b=FAKE, y=FAKE, yd=BF, M=5, s=12):
@@ -293,16 +278,10 @@ def test_use_device_mlps_refuses_what_does_not_fit_and_leaves_the_rest_alone():
 
 
 def test_mlp_train_kernels_use_no_scratch_and_do_not_spill():
-    from brepgen_amd import build as b
-    assert "mlp_train.hip" in b.SOURCES
-    r = subprocess.run([b._hipcc(), *b.FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(b.CSRC, "mlp_train.hip"),
-                        "-o", os.devnull], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    vals = [int(v) for key in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill", "SGPRs Spill") for v in re.findall(key + r": (\d+)", r.stderr)]
+    names, scratch, spills, sspills = resource_usage("mlp_train.hip")
     # 3 expansions, 2 contractions, 2 weight gradients and their reduction, 7 + 14 LN + SiLU row kernels, the loss gradient
-    assert len(names) == 30 and len(vals) == 90, names
-    assert all(v == 0 for v in vals), list(zip(names, vals))
+    assert len(names) == 30, names
+    assert all(v == 0 for v in scratch + spills + sspills), list(zip(names, scratch, spills, sspills))
     assert not any("lt_ln_reduce" in n for n in names)                         # the fp64 merge of the LayerNorm sums stays layer_train.hip's
 
 

@@ -1,6 +1,7 @@
-"""What the GPU tests of the training ops share (test_gpu_attn_bwd.py, test_gpu_linear_bwd.py, test_gpu_layer_train.py): the error
-pairs against fp64 and the `<= 2 x torch` yardstick, the parity-JSON record of a run, bit comparison, the 2-layer encoder and the
-gradients of an encoder.  TEST INFRASTRUCTURE; where the files differed in a detail, the detail is a parameter."""
+"""What the GPU tests of the training ops share (test_gpu_attn_bwd.py, test_gpu_linear_bwd.py, test_gpu_layer_train.py,
+test_gpu_mlp_train.py, test_gpu_conv_train.py): the error pairs against fp64 and the `<= 2 x torch` yardstick, the parity-JSON record
+of a run, bit comparison, the 2-layer encoder and the gradients of an encoder.  TEST INFRASTRUCTURE; where the files differed in a
+detail, the detail is a parameter.  Their CPU-side counterpart is tests/train_cpu.py."""
 import json
 import os
 

@@ -23,12 +23,11 @@ every call (forward, backward) between its own pair of device events; reported i
 
     python tools/attn_bwd_bench.py [--iters 20 --rounds 5 --warmup 5 --out profiles/r13/attn_bwd_bench.json]
 """
-import argparse
 import json
 import os
 import sys
 
-from bench_common import med, phases, run_children
+from bench_common import med, phases, train_bench_main
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -127,19 +126,10 @@ def child(B, N, iters, rounds, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per shape (child process)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13", "attn_bwd_bench.json"))
-    ap.add_argument("--child", nargs=2, type=int, default=None, help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.child:
-        print("ROWS " + json.dumps(child(args.child[0], args.child[1], args.iters, args.rounds, args.warmup)))
-        return 0
-    return run_children(__file__, SHAPES, ("B", "N"), ("--iters", args.iters, "--rounds", args.rounds, "--warmup", args.warmup), args.timeout,
-                        args.out, {"mfma_peak_flops": MFMA_PEAK, "iters_per_round": args.iters, "rounds": args.rounds})
+    return train_bench_main(__file__, os.path.join(ROOT, "profiles", "r13", "attn_bwd_bench.json"), SHAPES, ("B", "N"),
+                            lambda B, N, a: child(B, N, a.iters, a.rounds, a.warmup),
+                            lambda a: {"mfma_peak_flops": MFMA_PEAK, "iters_per_round": a.iters, "rounds": a.rounds},
+                            iters=20, warmup=5, timeout=300)
 
 
 if __name__ == "__main__":

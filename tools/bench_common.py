@@ -1,5 +1,7 @@
-"""What the bench tools share: the median, the two alternated device-event timers, the device's state, and the parent loop that runs
-one time-limited child process per shape.  Imports neither torch nor the package: the parent of a bench never touches the device."""
+"""What the bench tools share: the median, the two alternated device-event timers, the device's state, the parent loop that runs
+one time-limited child process per shape, and the command line of the training benches around it.  Imports neither torch nor the
+package: the parent of a bench never touches the device."""
+import argparse
 import json
 import os
 import subprocess
@@ -78,3 +80,26 @@ def run_children(script, shapes, names, options, timeout, out, head):
         json.dump({**head, "rows": rows, "failed": failed}, f, indent=1)
     print(json.dumps({"out": out, "rows": len(rows), "failed": failed is not None}))
     return 1 if failed else 0
+
+
+def train_bench_main(script, out, shapes, names, child, head, launches=None, iters=None, warmup=2, timeout=240):
+    """The command line of a training bench: --launches (per timed window) or --iters (per round), whichever default is given,
+    --rounds, --warmup, --timeout (seconds per child), --out, and the hidden `--child <shape>` hand-off.  As a child: child(*shape,
+    args) -> the shape's rows (a shape's numbers arrive as ints), printed as the ROWS line.  Otherwise `run_children` over `shapes`
+    with head(args) as the head of the JSON file.  -> the exit status."""
+    window = "iters" if launches is None else "launches"
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--" + window, type=int, default=iters if launches is None else launches,
+                    help=None if launches is None else "launches per timed window (per kernel)")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=warmup)
+    ap.add_argument("--timeout", type=int, default=timeout, help="seconds per case (child process)")
+    ap.add_argument("--out", default=out)
+    ap.add_argument("--child", nargs=len(names), default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        shape = [int(v) if v.lstrip("-").isdigit() else v for v in args.child]
+        print("ROWS " + json.dumps(child(*shape, args)))
+        return 0
+    options = ("--" + window, getattr(args, window), "--rounds", args.rounds, "--warmup", args.warmup)
+    return run_children(script, shapes, names, options, args.timeout, args.out, head(args))

@@ -17,12 +17,10 @@ and stops at the first that fails).  Per shape, bf16:
 
     python tools/conv_train_bench.py [--launches 20 --rounds 5 --warmup 2 --out profiles/r18/conv_train_bench.json]
 """
-import argparse
-import json
 import os
 import sys
 
-from bench_common import phases, run_children, windows
+from bench_common import phases, train_bench_main, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -147,21 +145,10 @@ def child(what, hw, C, args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=20, help="launches per timed window (per kernel)")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per case (child process)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r18", "conv_train_bench.json"))
-    ap.add_argument("--child", nargs=3, default=None, help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.child:
-        print("ROWS " + json.dumps(child(args.child[0], int(args.child[1]), int(args.child[2]), args)))
-        return 0
     cases = [(what, hw, C) for what in ("kernels", "block") for hw, C in CASES]
-    return run_children(__file__, cases, ("what", "grid", "C"), ("--launches", args.launches, "--rounds", args.rounds, "--warmup", args.warmup),
-                        args.timeout, args.out, {"stream_rate_bytes_per_s": STREAM_RATE, "mfma_peak_flops": MFMA_PEAK, "batch": BATCH,
-                                                 "launches_per_window": args.launches, "rounds": args.rounds, "autocast": "bfloat16"})
+    return train_bench_main(__file__, os.path.join(ROOT, "profiles", "r18", "conv_train_bench.json"), cases, ("what", "grid", "C"), child,
+                            lambda a: {"stream_rate_bytes_per_s": STREAM_RATE, "mfma_peak_flops": MFMA_PEAK, "batch": BATCH,
+                                       "launches_per_window": a.launches, "rounds": a.rounds, "autocast": "bfloat16"}, launches=20)
 
 
 if __name__ == "__main__":

@@ -17,12 +17,10 @@ another and stops at the first that fails).  In a child:
 
     python tools/layer_train_bench.py [--launches 300 --rounds 5 --warmup 2 --out profiles/r15/layer_train_bench.json]
 """
-import argparse
-import json
 import os
 import sys
 
-from bench_common import phases, run_children, windows
+from bench_common import phases, train_bench_main, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -174,20 +172,10 @@ def child(B, N, args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=300, help="launches per timed window (per kernel)")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per token count (child process)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15", "layer_train_bench.json"))
-    ap.add_argument("--child", type=int, nargs=2, default=None, help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.child:
-        print("ROWS " + json.dumps([child(args.child[0], args.child[1], args)]))
-        return 0
-    return run_children(__file__, SHAPES, ("B", "N"), ("--launches", args.launches, "--rounds", args.rounds, "--warmup", args.warmup),
-                        args.timeout, args.out, {"stream_rate_bytes_per_s": STREAM_RATE, "launches_per_window": args.launches,
-                                                 "rounds": args.rounds, "dropout_p": P})
+    return train_bench_main(__file__, os.path.join(ROOT, "profiles", "r15", "layer_train_bench.json"), SHAPES, ("B", "N"),
+                            lambda B, N, args: [child(B, N, args)],
+                            lambda a: {"stream_rate_bytes_per_s": STREAM_RATE, "launches_per_window": a.launches, "rounds": a.rounds,
+                                       "dropout_p": P}, launches=300)
 
 
 if __name__ == "__main__":

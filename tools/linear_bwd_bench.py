@@ -19,12 +19,11 @@ between its own pair of device events on one stream; reported is the median roun
 
     python tools/linear_bwd_bench.py [--iters 20 --rounds 5 --warmup 3 --out profiles/r14/linear_bwd_bench.json]
 """
-import argparse
 import json
 import os
 import sys
 
-from bench_common import device_state, phases, run_children
+from bench_common import device_state, phases, train_bench_main
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -117,20 +116,10 @@ def child(M, iters, rounds, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per token count (child process)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14", "linear_bwd_bench.json"))
-    ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.child:
-        print("ROWS " + json.dumps(child(args.child, args.iters, args.rounds, args.warmup)))
-        return 0
-    return run_children(__file__, [(M,) for M in TOKENS], ("M",), ("--iters", args.iters, "--rounds", args.rounds, "--warmup", args.warmup),
-                        args.timeout, args.out, {"mfma_peak_flops": MFMA_PEAK, "hbm_stream_rate": HBM_RATE, "iters_per_round": args.iters,
-                                                 "rounds": args.rounds})
+    return train_bench_main(__file__, os.path.join(ROOT, "profiles", "r14", "linear_bwd_bench.json"), [(M,) for M in TOKENS], ("M",),
+                            lambda M, a: child(M, a.iters, a.rounds, a.warmup),
+                            lambda a: {"mfma_peak_flops": MFMA_PEAK, "hbm_stream_rate": HBM_RATE, "iters_per_round": a.iters, "rounds": a.rounds},
+                            iters=20, warmup=3)
 
 
 if __name__ == "__main__":

@@ -16,13 +16,11 @@ and stops at the first that fails).
 
     python tools/mlp_train_bench.py [--launches 100 --rounds 5 --warmup 2 --out profiles/r17/mlp_train_bench.json]
 """
-import argparse
-import json
 import math
 import os
 import sys
 
-from bench_common import phases, run_children, windows
+from bench_common import phases, train_bench_main, windows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -195,21 +193,9 @@ def child(what, B, S, E, args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=100, help="launches per timed window (per kernel)")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per case (child process)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r17", "mlp_train_bench.json"))
-    ap.add_argument("--child", nargs=4, default=None, help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    if args.child:
-        what, B, S, E = args.child[0], int(args.child[1]), int(args.child[2]), int(args.child[3])
-        print("ROWS " + json.dumps(child(what, B, S, E, args)))
-        return 0
-    return run_children(__file__, CASES, ("what", "B_or_M", "S", "E"), ("--launches", args.launches, "--rounds", args.rounds, "--warmup", args.warmup),
-                        args.timeout, args.out, {"stream_rate_bytes_per_s": STREAM_RATE, "launches_per_window": args.launches,
-                                                 "rounds": args.rounds, "dropout_p": P, "autocast": "bfloat16"})
+    return train_bench_main(__file__, os.path.join(ROOT, "profiles", "r17", "mlp_train_bench.json"), CASES, ("what", "B_or_M", "S", "E"), child,
+                            lambda a: {"stream_rate_bytes_per_s": STREAM_RATE, "launches_per_window": a.launches, "rounds": a.rounds,
+                                       "dropout_p": P, "autocast": "bfloat16"}, launches=100)
 
 
 if __name__ == "__main__":
