@@ -3,7 +3,9 @@
 There is NO fallback: if the library is missing the import of any compute entry point raises.  The product
 path never touches ``oracle/`` or torch math for the work the HIP kernels do.
 """
+import contextlib
 import ctypes as C
+import enum
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -246,10 +248,10 @@ def load():
             fn.restype, fn.argtypes = res, args
         if lib.bg_abi_version() != ABI_VERSION:
             raise BrepgenHipError("libbrepgen_hip.so ABI version mismatch")
-        for kv in filter(None, os.environ.get("BG_TUNE", "").split(",")):     # A/B knobs, e.g. BG_TUNE="0=10,5=1"
-            k, v = kv.split("=")
-            lib.bg_tune_set(int(k), int(v))
-        _lib = lib
+        at_load = parse_tune(os.environ.get("BG_TUNE", ""))      # A/B knobs, e.g. BG_TUNE="P256_MODE=2,13=1".  Read BEFORE the library
+        _lib = lib                                               # is published: a bad string raises at every load(), none of it applied
+        for key, value in at_load.items():
+            _tune_set(key, value)
     return _lib
 
 
@@ -257,6 +259,59 @@ def check(rc, what):
     if rc != 0:
         msg = load().bg_last_error().decode(errors="replace")
         raise BrepgenHipError(f"{what} failed (code {rc}): {msg}")
+
+
+class Tune(enum.IntEnum):
+    """enum bg_tune_key of include/brepgen_hip.h, which describes every key (0 always = the library's own choice)"""
+    GEMM_STAGGER = 8
+    P256_MODE = 10
+    SPLIT_PIPE = 12
+    QKV_ATTN = 13
+    QKV_WALK = 14
+    SMALL_TILES = 15
+    FFN_FUSED = 16
+    VAE_GN1_FUSED = 19
+    ATTN_WALK = 20
+
+
+_tuned = {}        # Tune -> the value in force, of every key this process has set (the library starts with 0 everywhere and has no getter:
+#                    _tune_set below is the only caller of bg_tune_set with a valid key on the package's library -- a tripwire in
+#                    tests/test_abi_cpu.py -- so the record is exact)
+
+
+def _tune_key(key):
+    """Tune of a member, its name, its number or the number as a string"""
+    try:
+        return Tune(int(key)) if isinstance(key, int) or key.lstrip("-").isdigit() else Tune[key]
+    except (KeyError, ValueError):
+        raise BrepgenHipError(f"bg_tune: unknown key {key!r} (the keys: {', '.join(f'{k.name} = {int(k)}' for k in Tune)})") from None
+
+
+def _tune_set(key, value):
+    key = _tune_key(key)
+    check(load().bg_tune_set(int(key), int(value)), f"bg_tune_set({key.name}, {value})")
+    _tuned[key] = int(value)
+
+
+def parse_tune(text):
+    """"P256_MODE=2,13=1" -> {Tune.P256_MODE: 2, Tune.QKV_ATTN: 1}: the one parser of BG_TUNE and of the tools' command lines"""
+    return {_tune_key(k.strip()): int(v) for k, v in (kv.split("=") for kv in filter(None, text.split(",")))}
+
+
+@contextlib.contextmanager
+def tune(parsed=(), **settings):
+    """`with tune(P256_MODE=2, SMALL_TILES=-1): ...` (or `with tune(parse_tune(text)): ...`) -- kernel-selection knobs (process-global)
+    for the length of a block.  Yields the setter `set_key(key, value)` for further changes inside the block; on exit, by exception
+    too, EVERY key is back at the value that was in force on entry, so blocks nest."""
+    entry = dict(_tuned)
+    try:
+        for key, value in {**dict(parsed), **settings}.items():
+            _tune_set(key, value)
+        yield _tune_set
+    finally:
+        for key, value in list(_tuned.items()):
+            if value != entry.get(key, 0):
+                _tune_set(key, entry.get(key, 0))
 
 
 def ptr(t):

@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256, 3) void attn16_long_kernel(const void* __restr
     // by +- 15 % at the bench's edge batches and the launch lasted as long as the heaviest eighth.)
     int unit = ((int)(blockIdx.x >> 3) / nqb) * 8 + (int)(blockIdx.x & 7);
     const int qb = (int)(blockIdx.x >> 3) % nqb;
-    if (eighths) {                                       // (bg_tune key 20 = 1: the walk of rounds 2-5, for the in-process A/B)
+    if (eighths) {                                       // (BG_TUNE_ATTN_WALK = 1: the walk of rounds 2-5, for the in-process A/B)
         const int upx = (int)(gridDim.x >> 3) / nqb;     // units per XCD of the padded grid
         unit = (int)(blockIdx.x & 7) * upx + (int)(blockIdx.x >> 3) / nqb;
     }
@@ -561,7 +561,7 @@ int attention(const void* qkv, const uint8_t* key_pad, void* out, int B, int N, 
             const int nqb = (N + 127) / 128;
             const dim3 grid((unsigned)(nqb * 8 * ((B * BG_N_HEAD + 7) / 8)));
             const bool masked = key_pad != nullptr && offsets == nullptr;
-            const int eighths = g_tune[TUNE_ATTN_WALK] == 1;
+            const int eighths = g_tune[BG_TUNE_ATTN_WALK] == 1;
             with_bools(f16, masked, [&](auto F16, auto MASKED) {
                 hipLaunchKernelGGL((attn16_long_kernel<F16(), MASKED()>), grid, dim3(256), 0, s, qkv, key_pad, out, B, N, nqb, offsets, eighths);
             });

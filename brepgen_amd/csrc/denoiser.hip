@@ -191,7 +191,7 @@ static int encoder_layer_folded(const Ctx& c, const bg_layer_weights& L) {
     split_residual_in(op, c.XH, c.XL, 768);
     token_rows(c, op);
     if ((rc = gemm(op, c.dtype, c.s))) return rc;
-    if (L.w_1f && L.w_2f && g_tune[TUNE_FFN_FUSED] != 1) {
+    if (L.w_1f && L.w_2f && g_tune[BG_TUNE_FFN_FUSED] != 1) {
         // FFN1 + ReLU + FFN2 + residual as one launch: the [M, 1024] hidden tensor stays in the CU's LDS (ffn_fused.hip; bit-identical)
         FfnArgs ff{c.XH, c.XL, c.stats, L.w_1f, L.b_1, L.w1_colsum, L.w_2f, L.b_2, M, M, c.m_dev, 1e-5f};      // (statistics stride = the launch's row bound, as the GEMMs')
         BG_REQUIRE(ffn_fused_eligible(ff, c.dtype), BG_E_ARG, "bg_denoiser_fwd: w_1f / w_2f given, but the fused FFN launch does not apply");
@@ -240,10 +240,10 @@ static int bind_workspace(Ctx& c, const bg_denoiser_weights* w, const bg_denoise
     c.cvec = reinterpret_cast<float*>(c.ws + c.p.off_small) + (size_t)4 * B * 768;
     // variable-length execution: the valid tokens are compacted (row count stays on the device)
     c.varlen = in->varlen != 0 && in->mask != nullptr && net != BG_SURFPOS;
-    // ragged batches of short sequences: slot-packed rows + the fused QKV / attention launch (bg_tune key 13 = 1: dense packing +
+    // ragged batches of short sequences: slot-packed rows + the fused QKV / attention launch (BG_TUNE_QKV_ATTN = 1: dense packing +
     // GEMM + attention, the bit-equality baseline)
     c.paired = c.varlen && slot_packing_applies(net, B, S, E, w->dtype) && w->n_layer > 0 && w->layers[0].qkv_colsum != nullptr &&
-               g_tune[TUNE_QKV_ATTN] != 1;
+               g_tune[BG_TUNE_QKV_ATTN] != 1;
     c.M = c.paired ? c.p.Mrow : c.p.M;
     c.fold = w->dtype != BG_F32 && w->n_layer > 0 && w->layers[0].qkv_colsum != nullptr;
     if (c.fold) {
@@ -359,9 +359,9 @@ static int encoder_layers(Ctx& c) {
         c.key_pad = mexp;
     }
     BG_REQUIRE(!c.paired || c.fold, BG_E_ARG, "bg_denoiser_fwd: slot-packed execution needs the LayerNorm-fold operands");
-    c.fused_qkv = c.fold && !c.varlen && g_tune[TUNE_QKV_ATTN] != 1 &&
+    c.fused_qkv = c.fold && !c.varlen && g_tune[BG_TUNE_QKV_ATTN] != 1 &&
                   qkv_attn_eligible(c.B, c.N, c.dtype, c.stats, w->layers[0].qkv_colsum, w->layers[0].b_qkv) &&
-                  (g_tune[TUNE_QKV_ATTN] == 2 || qkv_attn_worthwhile(c.B, c.N));
+                  (g_tune[BG_TUNE_QKV_ATTN] == 2 || qkv_attn_worthwhile(c.B, c.N));
     for (int li = 0; li < w->n_layer; ++li)
         if ((rc = c.fold ? encoder_layer_folded(c, w->layers[li]) : encoder_layer_unfolded(c, w->layers[li]))) return rc;
     return 0;
@@ -458,7 +458,7 @@ static SplitState* split_state() {
 extern "C" int bg_slot_packing_applies(int net, int B, int S, int E, int dtype, int fold) {
     // the predicate bg_denoiser_fwd itself evaluates for a variable-length call (`paired`), for hosts that want to compute rows_plan
     if (net < BG_EDGEPOS) E = 1;
-    return (bg::slot_packing_applies(net, B, S, E, dtype) && fold != 0 && bg::g_tune[bg::TUNE_QKV_ATTN] != 1) ? 1 : 0;
+    return (bg::slot_packing_applies(net, B, S, E, dtype) && fold != 0 && bg::g_tune[BG_TUNE_QKV_ATTN] != 1) ? 1 : 0;
 }
 
 extern "C" size_t bg_workspace_bytes(int net, int B, int S, int E, int dtype) {

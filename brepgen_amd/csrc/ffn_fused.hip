@@ -68,12 +68,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
 
     if (threadIdx.x < 256) reinterpret_cast<float4*>(cst)[threadIdx.x] = reinterpret_cast<const float4*>(g.b1)[threadIdx.x];
 
-    int n_stamp = 0;
-    auto stamp = [&]() {
-        if (g.stamps && blockIdx.x == 0 && threadIdx.x == 0 && n_stamp < 32) g.stamps[n_stamp] = (long long)__builtin_amdgcn_s_memtime();
-        ++n_stamp;
-    };
-
     // the x panel of a row block on its way to the LDS: 64 rows x 1536 B = 12 x 16 B per thread, rows past the end clamped (never
     // stored).  Requested one panel AHEAD (during epilogue 2 of the previous panel), parked in registers, written after the barrier
     // that retires the hidden panel.
@@ -125,7 +119,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
         const bool has_next = p + (int)gridDim.x < n_panel;
         const int r0n = has_next ? (p + (int)gridDim.x) * FF_ROWS : r0;   // (no next panel: this one again -- loads whose results are never used.
         //  Unconditional on purpose: behind a branch the OLD registers would stay live through both K loops, as the value of the other path)
-        stamp();
         // Everything lane-dependent is derived from an OPAQUE thread id inside the panel loop: hoisted out of it, these addresses
         // would be live across both K loops, which run near the register limit, and be spilled (hipcc answers every scratch reload
         // with s_waitcnt vmcnt(0): the weight stream's loads in flight would be drained).
@@ -136,7 +129,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
         const unsigned lane16 = (unsigned)ln * 16u;
         FF_PANEL_STORE()
         __syncthreads();
-        stamp();
 
         // ---- phase 1: h = x W1'^T, wave w: hidden columns 128 w .. + 127 ----
         f32x16 acc1[2][4];
@@ -177,7 +169,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
                 ldx(0, s + 4); mm(3, 1); ldw(3, s + 7);
             }
         }
-        stamp();
         // the lane's 64 column sums of W1' travel while the workgroup gathers at the barrier (the weight registers are free now)
         float4 csum[4][4];
 #pragma unroll
@@ -186,7 +177,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
             for (int q = 0; q < 4; ++q) csum[j][q] = *reinterpret_cast<const float4*>(g.colsum1 + wave * 128 + j * 32 + 8 * q + 4 * hq);
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();                                            // every wave is done with the x panel: h may overwrite it
-        stamp();
 
         // ---- epilogue 1: LayerNorm fold + bias + ReLU -> 16 bits -> the hidden panel (row-major, same swizzle) ----
 #pragma unroll
@@ -210,7 +200,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
             }
         coeffs(r0n, cf);                              // (the fold coefficients of this panel are consumed; the next panel's rows are untouched by this launch)
         __syncthreads();
-        stamp();
 
         // ---- phase 2: y = h W2^T, wave w: output columns 96 w .. + 95 ----
         // Epilogue-2 bookkeeping first: the residual octets of its first three slabs are requested HERE, before the K loop (48
@@ -274,7 +263,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
                 }
             }
         }
-        stamp();
         // (no barrier: the epilogue below works out of the wave's private patch; the hidden panel is retired by the barrier at its end)
 
         // ---- epilogue 2: split residual + statistics, wave-private, eight slabs of 8 rows x 96 fp32 columns ----
@@ -338,7 +326,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        stamp();
         __syncthreads();                                            // hidden panel and patches retired; every half-group partial is in place
         if (threadIdx.x < 256) {
             const int pi = threadIdx.x >> 6, row = threadIdx.x & 63;
@@ -347,7 +334,6 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(FfnArgs g) {
             const int grow = r0 + row;
             if (grow < Mv) reinterpret_cast<float2*>(g.stats)[(size_t)(3 * pi + 1) * g.m_stride + grow] = make_float2(a.x + b.x, a.y + b.y);
         }
-        stamp();
     }
 }
 
@@ -365,10 +351,8 @@ int ffn_fused(const FfnArgs& g, int dtype, hipStream_t s, double rows_hint) {
     // algorithmic cost: both products; bytes = x_hi rows in + (hi, lo) residual in and out + statistics in and out + the weights once
     ProfScope ps(PK_FFN_FUSED, 2.0 * rows * (double)FF_D * FF_H * 2.0,
                  rows * (FF_D * 2.0 * 5 + 2 * 12 * 8.0) + 2.0 * FF_D * FF_H * 2.0 + (FF_H * 2 + FF_D) * 4.0, s);
-    FfnArgs a = g;
-    a.stamps = reinterpret_cast<long long*>(((uintptr_t)(unsigned)g_tune[TUNE_DEBUG_PTR_HI] << 32) | (uintptr_t)(unsigned)g_tune[TUNE_DEBUG_PTR_LO]);
-    if (dtype == BG_F16) hipLaunchKernelGGL((ffn_fused_kernel<true>), dim3(grid), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((ffn_fused_kernel<false>), dim3(grid), dim3(512), 0, s, a);
+    if (dtype == BG_F16) hipLaunchKernelGGL((ffn_fused_kernel<true>), dim3(grid), dim3(512), 0, s, g);
+    else hipLaunchKernelGGL((ffn_fused_kernel<false>), dim3(grid), dim3(512), 0, s, g);
     return launch_status("ffn_fused");
 }
 

@@ -743,17 +743,17 @@ static void gemm_cost(const GemmArgs& g, double rows, double& flops, double& byt
     if (g.stats_in) bytes += 8.0 * rows * (g.K / G_BK) + 4.0 * g.N;   // LayerNorm fold: the row partials + column sums
 }
 
-// phase-group delay of a split-residual launch on the 256 x 256 kernel (bg_tune key 8: > 0 = that many x 1024 cycles, < 0 = off;
+// phase-group delay of a split-residual launch on the 256 x 256 kernel (BG_TUNE_GEMM_STAGGER: > 0 = that many x 1024 cycles, < 0 = off;
 // default: P256_SPLIT_STAGGER from P256_SPLIT_STAGGER_ROUNDS rounds of tiles on)
 static int split_stagger(const GemmArgs& g) {
-    const int t = g_tune[TUNE_GEMM_STAGGER];
+    const int t = g_tune[BG_TUNE_GEMM_STAGGER];
     if (t != 0) return t > 0 ? t : 0;
     const int nt_n = g.N_pad / 256, tiles = ((g.M + 255) / 256) * nt_n;
     return tiles >= P256_SPLIT_STAGGER_ROUNDS * ((256 / nt_n) * nt_n) ? P256_SPLIT_STAGGER : 0;
 }
 
-// Which kernel runs a 16-bit GEMM (every choice computes bit-identical results; the bg_tune keys named here exist so that the tests
-// can compare them -- key 10: 256-kernel mode, 12: split-residual kernel, 15: small-launch threshold, 8: phase-group delay):
+// Which kernel runs a 16-bit GEMM (every choice computes bit-identical results; the knobs named here exist so that the tests
+// can compare them -- BG_TUNE_P256_MODE, BG_TUNE_SPLIT_PIPE, BG_TUNE_SMALL_TILES, BG_TUNE_GEMM_STAGGER of enum bg_tune_key):
 //   narrow outputs (N % 128 != 0: fc_out.3, conv_out)            -> generic kernel, 128 x 64 tiles
 //   < SMALL_LAUNCH_TILES tiles of 128 x 128 (batch 16)            -> generic kernel, 64 x 64 tiles, 3-deep ring
 //   16-bit output, QKV / FFN1 shapes                              -> 256 x 256 kernel on the rows that fill whole rounds (p256_rows)
@@ -777,8 +777,8 @@ static int launch16(const GemmArgs& g, hipStream_t s) {
     // 128 x 128 tile per workgroup leaves most of the chip idle while every workgroup walks its 12 K-steps one DMA round trip at a
     // time.  64 x 64 tiles (two waves, 3-deep ring: two K-steps of DMA in flight) put four times as many workgroups on the chip
     // and halve the per-step latency chain; same k order, same epilogue code -> bit-identical results
-    // (tests/test_gpu_round4.py).  bg_tune key 15: tile-count threshold (0 = default, -1 = off).
-    const int small_nt = g_tune[TUNE_SMALL_TILES] < 0 ? 0 : (g_tune[TUNE_SMALL_TILES] > 0 ? g_tune[TUNE_SMALL_TILES] : SMALL_LAUNCH_TILES);
+    // (tests/test_gpu_round4.py).  BG_TUNE_SMALL_TILES: tile-count threshold (0 = default, -1 = off).
+    const int small_nt = g_tune[BG_TUNE_SMALL_TILES] < 0 ? 0 : (g_tune[BG_TUNE_SMALL_TILES] > 0 ? g_tune[BG_TUNE_SMALL_TILES] : SMALL_LAUNCH_TILES);
     if (g.cv_C == 0 && nt < small_nt && (g.stats_in == nullptr || g.K / G_BK <= 16)) {
         double fl, by;
         gemm_cost(g, rows_all, fl, by);
@@ -808,10 +808,10 @@ static int launch16(const GemmArgs& g, hipStream_t s) {
     }
     // 256 x 256 persistent kernel (gemm_p256.hip) on the row panels that fill complete rounds of tiles; a 128 x 128 kernel below
     // runs the remaining rows (bg_common.h: p256_rows).  With a device-side row count the split is only known on the device: both
-    // kernels are launched and evaluate the same rule.  bg_tune key 10: 0 = hybrid, 1 = 256 kernel alone wherever eligible, 2 = never.
+    // kernels are launched and evaluate the same rule.  BG_TUNE_P256_MODE: 0 = hybrid, 1 = 256 kernel alone wherever eligible, 2 = never.
     GemmArgs gt = g;                                              // what the 128 x 128 kernels below see
     gt.hybrid = 0;
-    if (g_tune[TUNE_P256_MODE] != 2 && p256_eligible(g)) {
+    if (g_tune[BG_TUNE_P256_MODE] != 2 && p256_eligible(g)) {
         const bool split = g.out_lo != nullptr;
         const int hmode = g.concurrent ? 2 : 1;
         // the 256 x 256 kernel on h's rows, booked as `rows` rows under the key of its kind (apart: HBM-bound vs MFMA-bound launches),
@@ -823,7 +823,7 @@ static int launch16(const GemmArgs& g, hipStream_t s) {
             if (split) h.p256_stagger = split_stagger(g);
             return launch_p256<F16>(h, s);
         };
-        if (g_tune[TUNE_P256_MODE] == 1) return p256(g, rows_all);
+        if (g_tune[BG_TUNE_P256_MODE] == 1) return p256(g, rows_all);
         // Host-side view of the row count: exact without m_dev; with a device-side count the caller's estimate (rows_hint: the
         // drop-in modules count the valid tokens once per mask) or else the bound M.  It only chooses between "both kernels, the
         // device evaluates the rule" and "the 128 kernel alone, no rule" -- either is correct for any actual row count.
@@ -857,8 +857,8 @@ static int launch16(const GemmArgs& g, hipStream_t s) {
     double fl_t, by_t;
     gemm_cost(g, rows_tail, fl_t, by_t);
     // residual-stream GEMMs of the encoder layers: the software-pipelined split kernel (gemm_split.hip) takes the rows the 256 x 256
-    // kernel does not (bg_tune key 12 = 1: the 128 x 128 persistent kernel's split epilogue instead, for the bit-equality tests)
-    if (g_tune[TUNE_SPLIT_PIPE] != 1 && split_pipe_eligible(g_)) {
+    // kernel does not (BG_TUNE_SPLIT_PIPE = 1: the 128 x 128 persistent kernel's split epilogue instead, for the bit-equality tests)
+    if (g_tune[BG_TUNE_SPLIT_PIPE] != 1 && split_pipe_eligible(g_)) {
         ProfScope prof(PK_GEMM_SPLIT, fl_t, by_t, s);
         return launch_split_pipe<F16>(g_, s);
     }

@@ -561,10 +561,10 @@ bool qkv_attn_worthwhile(int B, int N) {
 }
 
 // the XCD-pinned walk needs whole octets of workgroups (block b runs on XCD b % 8) and pays from two rounds of tiles on: below that the
-// XCDs' shares (a quarter of the sample groups x 6 heads each) are too uneven (37 samples x 60 tokens: 20.7 -> 34.6 us).  bg_tune key
-// 14: 1 = never, 2 = wherever the grid allows (the bit-equality tests).
+// XCDs' shares (a quarter of the sample groups x 6 heads each) are too uneven (37 samples x 60 tokens: 20.7 -> 34.6 us).
+// BG_TUNE_QKV_WALK: 1 = never, 2 = wherever the grid allows (the bit-equality tests).
 static int qkv_attn_pinned_walk(int tiles, int grid) {
-    const int t = g_tune[TUNE_QKV_WALK];
+    const int t = g_tune[BG_TUNE_QKV_WALK];
     if (t == 1 || (grid & 7) != 0) return 0;
     return (t == 2 || tiles >= 512) ? 1 : 0;
 }

@@ -22,7 +22,12 @@ int launch_status(const char* what) {
     return (int)e;
 }
 
-int g_tune[TUNE_COUNT] = {0};
+int g_tune[BG_TUNE_ATTN_WALK + 1] = {0};
+template <int N> constexpr bool all_below(const int (&keys)[N], int bound) {
+    for (int i = 0; i < N; ++i)
+        if (keys[i] < 0 || keys[i] >= bound) return false;
+    return true;
+}
 
 // ---- per-kernel event timing ------------------------------------------------------------------------------
 bool g_prof_on = false;
@@ -92,9 +97,17 @@ extern "C" int bg_profile_end(bg_profile_row* rows, int max_rows) {
 }
 
 extern "C" int bg_tune_set(int key, int value) {
-    BG_REQUIRE(key >= 0 && key < bg::TUNE_COUNT, BG_E_ARG, "bg_tune_set: unknown key %d", key);
-    bg::g_tune[key] = value;
-    return 0;
+    // the enumerators of bg_tune_key, and nothing between or beyond them (a new key: the enum, this list; the table's size is checked)
+    static constexpr int keys[] = {BG_TUNE_GEMM_STAGGER, BG_TUNE_P256_MODE, BG_TUNE_SPLIT_PIPE, BG_TUNE_QKV_ATTN, BG_TUNE_QKV_WALK,
+                                   BG_TUNE_SMALL_TILES, BG_TUNE_FFN_FUSED, BG_TUNE_VAE_GN1_FUSED, BG_TUNE_ATTN_WALK};
+    static_assert(bg::all_below(keys, (int)(sizeof(bg::g_tune) / sizeof(bg::g_tune[0]))), "a bg_tune_key past the end of g_tune");
+    for (const int k : keys)
+        if (k == key) {
+            bg::g_tune[key] = value;
+            return 0;
+        }
+    bg::set_error("bg_tune_set: unknown key %d", key);
+    return BG_E_ARG;
 }
 
 extern "C" int bg_gemm_p256_rows(int rows, int n_cols, int split_residual, int concurrent) {

@@ -169,7 +169,7 @@ extern "C" int bg_vae_run(const bg_vae_op* ops, int n_ops, int n_slots, int in_h
             // GroupNorm(1, C) over a sample one wave can hold (the 1-D VAE's blocks): statistics + normalisation + activation in ONE pass
             // wherever the normalised tensor is produced by a 1x1 gather (everything but a materialised im2col over a window)
             const bool window_gather = o.op == BG_VOP_CONV && !conv_implicit_ok(o, in, S) && (o.kh * o.kw > 1 || o.stride != 1 || o.up != 0 || o.pad_mode != 0);
-            const bool gn1 = o.gn_gamma && o.gn_groups == 1 && !window_gather && g_tune[TUNE_VAE_GN1_FUSED] != 1 &&
+            const bool gn1 = o.gn_gamma && o.gn_groups == 1 && !window_gather && g_tune[BG_TUNE_VAE_GN1_FUSED] != 1 &&
                              gn1_norm_act_supported(P, in.C);
             if (o.gn_gamma) {
                 stats = reinterpret_cast<float*>(sc);

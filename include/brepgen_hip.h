@@ -538,7 +538,7 @@ typedef struct {
 } bg_denoiser_inputs;
 
 /* 1 when a variable-length call of bg_denoiser_fwd with these shapes runs SLOT-PACKED (64-row slots of one or two samples, the fused QKV +
- * attention launch): the library's own predicate (net, shapes, 16-bit dtype, LayerNorm-fold weights given = `fold`, bg_tune key 13),
+ * attention launch): the library's own predicate (net, shapes, 16-bit dtype, LayerNorm-fold weights given = `fold`, BG_TUNE_QKV_ATTN),
  * exported so that a host that fills bg_denoiser_inputs.rows_plan counts the rows of the layout the library will actually use.
  * rows_plan only ever chooses between launch plans that are all correct for any row count: it must never be used to skip work. */
 int bg_slot_packing_applies(int net, int B, int S, int E, int dtype, int fold);
@@ -704,23 +704,34 @@ int bg_profile_end(bg_profile_row* rows, int max_rows);   /* returns the number 
 int bg_allgather(const void* send, void* recv, size_t bytes_per_rank, void* nccl_comm, bg_stream_t stream);
 
 /* Kernel-selection knobs.  Every choice computes bit-identical results: the keys exist so that the parity tests can run the same
- * GEMM on each kernel that may serve it (0 always = the library's own choice; process-global, not for production use).
- *   key  8  split-residual launches on the 256 x 256 kernel: start delay of the second phase group, x 1024 cycles (< 0: none)
- *   key 10  256 x 256 persistent kernel: 1 = alone wherever eligible, 2 = never
- *   key 12  split-residual GEMMs of the encoder layers: 1 = the 128 x 128 persistent kernel instead of the pipelined one
- *   key 13  QKV + attention of short, equally long sequences: 1 = as two launches (GEMM, attention) instead of the fused kernel,
- *           2 = fused wherever eligible (the library's own choice leaves a nearly empty second round of tiles to the two launches)
- *   key 14  tile walk of that fused kernel: 1 = plain (every XCD runs all 12 heads), 2 = XCD-pinned head halves wherever the grid
- *           allows (the library's own choice: from two rounds of tiles on)
- *   key 15  small launches: tile-count threshold of the 64 x 64-tile path (< 0: off)
- *   key 16  FFN1 / FFN2 of layers that carry w_1f / w_2f: 1 = as two GEMM launches instead of the fused launch (bg_ffn_fused_fwd)
- *   keys 17 / 18  measurement aid: low / high 32 bits of a device address that receives s_memtime stamps of the fused FFN launch's
- *           phases (tools/ffn_fused_bench.py stamps); 0 / 0 = off
- *   key 19  bg_vae_run, GroupNorm(1, C) over samples of 2048 / 4096 values (the 1-D VAE's blocks): 1 = statistics pass + gather as two
- *           launches (bg_groupnorm_stats, bg_im2col) instead of the one-pass kernel
- *   key 20  long-sequence attention: 1 = each XCD walks a contiguous eighth of the (sample, head) units (rounds 2-5) instead of the
- *           units going round-robin over the XCDs (ragged batches: the eighths' shares of sum n_b^2 differ, the launch lasts as long
- *           as the heaviest) */
+ * work on each kernel that may serve it, and so that two kernels can be timed against each other in one process (value 0 always =
+ * the library's own choice; process-global, not for production use).  The numbers are frozen: they appear in recorded logs and in
+ * BG_TUNE strings.  bg_tune_set refuses every key that has no enumerator here with BG_E_ARG; values are not constrained. */
+enum bg_tune_key {
+    /* split-residual launches on the 256 x 256 kernel: start delay of the second phase group, x 1024 cycles (< 0: none) */
+    BG_TUNE_GEMM_STAGGER = 8,
+    /* 256 x 256 persistent kernel: 1 = alone wherever eligible, 2 = never */
+    BG_TUNE_P256_MODE = 10,
+    /* split-residual GEMMs of the encoder layers: 1 = the 128 x 128 persistent kernel instead of the pipelined one */
+    BG_TUNE_SPLIT_PIPE = 12,
+    /* QKV + attention of short, equally long sequences: 1 = as two launches (GEMM, attention) instead of the fused kernel, 2 = fused
+     * wherever eligible (the library's own choice leaves a nearly empty second round of tiles to the two launches) */
+    BG_TUNE_QKV_ATTN = 13,
+    /* tile walk of that fused kernel: 1 = plain (every XCD runs all 12 heads), 2 = XCD-pinned head halves wherever the grid allows
+     * (the library's own choice: from two rounds of tiles on) */
+    BG_TUNE_QKV_WALK = 14,
+    /* small launches: tile-count threshold of the 64 x 64-tile path (< 0: off) */
+    BG_TUNE_SMALL_TILES = 15,
+    /* FFN1 / FFN2 of layers that carry w_1f / w_2f: 1 = as two GEMM launches instead of the fused launch (bg_ffn_fused_fwd) */
+    BG_TUNE_FFN_FUSED = 16,
+    /* bg_vae_run, GroupNorm(1, C) over samples of 2048 / 4096 values (the 1-D VAE's blocks): 1 = statistics pass + gather as two
+     * launches (bg_groupnorm_stats, bg_im2col) instead of the one-pass kernel */
+    BG_TUNE_VAE_GN1_FUSED = 19,
+    /* long-sequence attention: 1 = each XCD walks a contiguous eighth of the (sample, head) units (rounds 2-5) instead of the units
+     * going round-robin over the XCDs (ragged batches: the eighths' shares of sum n_b^2 differ, the launch lasts as long as the
+     * heaviest) */
+    BG_TUNE_ATTN_WALK = 20
+};
 int bg_tune_set(int key, int value);
 
 /* How a 16-bit GEMM launch of `rows` x `n_cols` (n_cols a multiple of 256) is partitioned between the 256 x 256

@@ -15,13 +15,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import pytest  # noqa: E402
 import torch  # noqa: E402
 
 import parity_cases as pc  # noqa: E402
 import hip_ops as ops  # noqa: E402
+from brepgen_amd import _lib  # noqa: E402
 
 F32, BF16 = torch.float32, torch.bfloat16
 QUICK = "--quick" in sys.argv
+
+
+@pytest.fixture
+def tune():
+    """The GPU tests' setter of the kernel-selection knobs, by name: tune("P256_MODE", 2).  The knobs are process-global; whatever the
+    test set or left behind, EVERY key is back at its value at entry afterwards (_lib.tune)."""
+    with _lib.tune() as set_key:
+        yield set_key
 
 
 def run(name, fn, *a, **k):

@@ -447,3 +447,81 @@ def test_shared_training_host_steps_are_written_once():
                 if train_cpu.RESOURCE_FLAG[1:] in fh.read():
                     with_report.append(f)
     assert with_report == ["train_cpu.py"], with_report
+
+
+# ---- the kernel-selection knobs (enum bg_tune_key, _lib.Tune / _lib.tune): no device work, so all of it is checked here -----------
+def test_tune_enum_matches_the_header():
+    """_lib.Tune is enum bg_tune_key of include/brepgen_hip.h, names and numbers both, and bg_tune_set accepts every member."""
+    header = open(os.path.join(ROOT, "include", "brepgen_hip.h")).read()
+    body = re.search(r"enum bg_tune_key \{(.*?)\};", header, flags=re.S).group(1)
+    declared = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bBG_TUNE_(\w+) = (\d+)", re.sub(r"/\*.*?\*/", "", body, flags=re.S))}
+    assert declared and declared == {k.name: int(k) for k in _lib.Tune}
+    with _lib.tune() as set_key:
+        for k in _lib.Tune:
+            set_key(k, 1)                                                 # (raises on a refusal; through _lib, which keeps the record)
+
+
+def test_tune_set_refuses_keys_without_a_name():
+    """The numbers between the enumerators (removed experiments; 17 / 18 once carried a device address) and everything outside them."""
+    lib = _lib.load()
+    for key in (-1, 0, 7, 9, 11, 17, 18, 21):
+        assert lib.bg_tune_set(key, 1) == _lib.BG_E_ARG, key
+        assert f"unknown key {key}".encode() in lib.bg_last_error(), key
+
+
+def test_tune_settings_end_with_their_block():
+    """bg_slot_packing_applies reads QKV_ATTN and does no device work: the setting holds inside `with _lib.tune(...)` and the value at
+    entry is back after it -- normal exit, exception, nested blocks; parse_tune reads names and numbers, and refuses others."""
+    lib = _lib.load()
+    packed = lambda: lib.bg_slot_packing_applies(_lib.BG_SURFZ, 8, 30, 1, _lib.BG_BF16, 1)
+    assert packed() == 1
+    with _lib.tune(QKV_ATTN=1):
+        assert packed() == 0
+    assert packed() == 1
+    with pytest.raises(ZeroDivisionError):
+        with _lib.tune(QKV_ATTN=1):
+            assert packed() == 0
+            1 / 0
+    assert packed() == 1
+    with _lib.tune(QKV_ATTN=1):
+        with _lib.tune(QKV_ATTN=1, P256_MODE=2):
+            assert packed() == 0
+        assert packed() == 0
+        with _lib.tune(QKV_ATTN=0):
+            assert packed() == 1
+        assert packed() == 0
+    assert packed() == 1
+    with _lib.tune() as set_key:                                          # the setter the GPU tests' `tune` fixture hands out
+        set_key("QKV_ATTN", 1)
+        assert packed() == 0
+    assert packed() == 1
+    for text in ("QKV_ATTN=1", "13=1", "P256_MODE=2,13=1"):
+        settings = _lib.parse_tune(text)
+        assert settings[_lib.Tune.QKV_ATTN] == 1 and all(isinstance(k, _lib.Tune) for k in settings)
+        with _lib.tune(settings):
+            assert packed() == 0
+        assert packed() == 1
+    assert _lib.parse_tune("") == {} and _lib.parse_tune("P256_MODE=2,13=1") == {_lib.Tune.P256_MODE: 2, _lib.Tune.QKV_ATTN: 1}
+    for bad in ("QKV_ATN=1", "17=1", "0=10"):
+        with pytest.raises(_lib.BrepgenHipError):
+            _lib.parse_tune(bad)
+    with pytest.raises(_lib.BrepgenHipError):
+        with _lib.tune(QKV_ATN=1):
+            pass
+    assert packed() == 1
+
+
+def test_only_the_binding_sets_knobs():
+    """_lib.tune can put every key back because _lib is the only caller of the library's setter: a tripwire against a test or tool that
+    goes round it -- any file under tests/ or tools/, any module of the package.  tools/gemm_split_ab_libs.py is the named exception
+    (it sets a knob of an OLD build of the library, which _lib does not hold), and this file, which hands the C function bad keys."""
+    found = []
+    for d, every_file in (("tests", True), ("tools", True), ("brepgen_amd", False)):
+        for path, dirs, files in os.walk(os.path.join(ROOT, d)):
+            dirs[:] = sorted(x for x in dirs if x != "__pycache__" and (every_file or x != "_build"))
+            for f in sorted(files):
+                if every_file or f.endswith(".py"):
+                    with open(os.path.join(path, f), "rb") as fh:
+                        if b"bg_tune_set" in fh.read():
+                            found.append(os.path.relpath(os.path.join(path, f), ROOT))
+    assert found == ["tests/test_abi_cpu.py", "tools/gemm_split_ab_libs.py", "brepgen_amd/_lib.py"], found

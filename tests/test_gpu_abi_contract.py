@@ -8,7 +8,7 @@ on the already-rounded operands (tests/parity_cases.py) under the tolerance the 
 
 Section A also asserts the kernel that served the call (bg_profile_begin / bg_profile_end report it), so that a dispatch change cannot
 silently move a case onto another kernel.  The profiler books the narrow 128 x 64 and the small-launch 64 x 64 instantiations of the
-generic kernel under one name, and the generic and the persistent 128 x 128 kernels under another; the bg_tune keys (10, 12, 15) and
+generic kernel under one name, and the generic and the persistent 128 x 128 kernels under another; the knobs P256_MODE, SPLIT_PIPE, SMALL_TILES and
 the strides select between those, as launch16 (csrc/gemm_16bit.hip) documents.  A strided call whose strides change only addresses
 (every stride a multiple of 8, same keys) must equal the dense call on the same operands bit for bit; where the strides change the
 dispatch (ldc = 770 / 772: scalar or 8-byte stores) only the fp64 tolerance is required and the bit comparison is printed.
@@ -17,6 +17,8 @@ import math
 
 import pytest
 import torch
+
+from gpu_check import tune  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,19 +37,6 @@ def pc():
         pytest.skip("needs a GPU")
     import parity_cases
     return parity_cases
-
-
-@pytest.fixture
-def tune():
-    """bg_tune_set with the keys this file touches (10: 256-kernel mode, 12: split-residual kernel, 15: small-launch threshold) back at
-    0 afterwards, whatever the test did: the keys are process-global."""
-    from brepgen_amd import _lib
-    lib = _lib.load()
-    try:
-        yield lib.bg_tune_set
-    finally:
-        for k in (10, 12, 15):
-            lib.bg_tune_set(k, 0)
 
 
 def _out_tol(e, out_dtype):
@@ -109,9 +98,9 @@ def test_small_launch_gemm_with_strides(pc, dt, M):
 @pytest.mark.parametrize("dt", [BF16, F16])
 @pytest.mark.parametrize("lda", [768, 776])
 def test_generic_128_gemm_with_strides_that_rule_out_the_persistent_kernels(pc, tune, dt, lda):
-    """Small-launch path off (key 15 = -1), 72 tiles: ldc = 772 (16-bit output, vector epilogue) and ld_add = 770 (fp32 output, scalar
+    """Small-launch path off (SMALL_TILES = -1), 72 tiles: ldc = 772 (16-bit output, vector epilogue) and ld_add = 770 (fp32 output, scalar
     epilogue with N == N_pad) are not persistent_ok and not p256_eligible -> the generic 128 x 128 kernel."""
-    tune(15, -1)
+    tune("SMALL_TILES", -1)
     e = pc.gemm_abi_case(1409, 768, 768, dt, lda=lda, ldc=772, out_dtype=dt)
     _check_plain(e, dt, K_128, f"generic lda={lda} ldc=772 16-bit", False)
     e = pc.gemm_abi_case(1409, 768, 768, dt, lda=lda, ld_add=770, add_mode="resid", out_dtype=F32)
@@ -148,9 +137,9 @@ def _check_split(e, dt, kernel, what, inplace, stats):
 
 @pytest.mark.parametrize("dt", [BF16, F16])
 def test_persistent_128_gemm_with_strides(pc, tune, dt):
-    """key 15 = -1, key 10 = 2: the persistent 128 x 128 kernel, lda = ldc = 776, once per compiled epilogue mode."""
-    tune(15, -1)
-    tune(10, 2)
+    """SMALL_TILES = -1, P256_MODE = 2: the persistent 128 x 128 kernel, lda = ldc = 776, once per compiled epilogue mode."""
+    tune("SMALL_TILES", -1)
+    tune("P256_MODE", 2)
     e = pc.gemm_abi_case(1409, 768, 768, dt, lda=776, ldc=776, out_dtype=dt)
     _check_plain(e, dt, K_128, "persistent plain 16-bit", True)
     e = pc.gemm_abi_case(1409, 768, 768, dt, lda=776, ldc=776, out_dtype=F32, add_mode="resid", ld_add=772)
@@ -159,7 +148,7 @@ def test_persistent_128_gemm_with_strides(pc, tune, dt):
     _check_plain(e, F32, K_128, "persistent general fp32, add aliases out", True, inplace=True)
     _check_fold(pc.gemm_fold_abi_case(1408, 768, dt, lda=776, ldc=776), dt, K_128, "persistent fold")
     _check_fold(pc.gemm_fold_abi_case(1408, 1024, dt, act=1, lda=776, ldc=1032), dt, K_128, "persistent fold + ReLU")
-    tune(12, 1)
+    tune("SPLIT_PIPE", 1)
     for inplace in (False, True):
         for stats in (True, False):
             e = pc.gemm_split_abi_case(1409, dt, lda=776, ldc=776, ld_res=784, inplace=inplace, want_stats=stats)
@@ -169,10 +158,10 @@ def test_persistent_128_gemm_with_strides(pc, tune, dt):
 @pytest.mark.parametrize("dt", [BF16, F16])
 @pytest.mark.parametrize("K", [768, 1024])
 def test_pipelined_split_gemm_with_strides(pc, tune, dt, K):
-    """csrc/gemm_split.hip (key 12 = 0): split output + split residual + statistics + bias; its LDS-DMA loads build 32-bit byte
+    """csrc/gemm_split.hip (SPLIT_PIPE = 0): split output + split residual + statistics + bias; its LDS-DMA loads build 32-bit byte
     offsets from lda.  Separate residual planes (ldc = 776, ld_res = 784) and the in-place form (ldc = ld_res = 776)."""
-    tune(15, -1)
-    tune(10, 2)
+    tune("SMALL_TILES", -1)
+    tune("P256_MODE", 2)
     lda = K + 8
     e = pc.gemm_split_abi_case(1409, dt, K=K, lda=lda, ldc=776, ld_res=784)
     _check_split(e, dt, K_SPLIT_PIPE, f"split pipe K={K} separate residual", False, True)
@@ -183,10 +172,10 @@ def test_pipelined_split_gemm_with_strides(pc, tune, dt, K):
 @pytest.mark.parametrize("dt", [BF16, F16])
 @pytest.mark.parametrize("M", [256, 510, 1408])
 def test_p256_gemm_with_strides(pc, tune, dt, M):
-    """csrc/gemm_p256.hip alone (key 10 = 1): plain and LayerNorm fold with and without ReLU at N = 768 / 1024 / 2304, split output
+    """csrc/gemm_p256.hip alone (P256_MODE = 1): plain and LayerNorm fold with and without ReLU at N = 768 / 1024 / 2304, split output
     with and without statistics, in place and not; lda = 776, ldc = N + 8, ld_res = N + 16."""
-    tune(15, -1)
-    tune(10, 1)
+    tune("SMALL_TILES", -1)
+    tune("P256_MODE", 1)
     for N in (768, 1024, 2304):
         for act in (0, 1):
             e = pc.gemm_abi_case(M, N, 768, dt, lda=776, ldc=N + 8, act=act, out_dtype=dt, seed=N)

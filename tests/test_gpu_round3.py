@@ -8,6 +8,8 @@ import os
 import pytest
 import torch
 
+from gpu_check import tune  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 
 F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
@@ -36,15 +38,6 @@ def _record(key, value):
         json.dump(d, f, indent=1, sort_keys=True)
 
 
-@pytest.fixture
-def tune():
-    """bg_tune_set with automatic reset of the 256-kernel mode (key 10)."""
-    from brepgen_amd import _lib
-    lib = _lib.load()
-    yield lib.bg_tune_set
-    lib.bg_tune_set(10, 0)
-
-
 # ---- the 256 x 256 persistent GEMM -------------------------------------------------------------------------------------
 def _gemm_cases(M, dt, seed=0):
     import hip_ops as ops
@@ -67,15 +60,15 @@ def _gemm_cases(M, dt, seed=0):
 @pytest.mark.parametrize("dt", [BF16, F16])
 @pytest.mark.parametrize("M", [1037, 1038, 256 * 7, 130, 17294])
 def test_p256_gemm_is_bit_identical_to_the_128_kernel(pc, tune, dt, M):
-    """Plain and LayerNorm-fold epilogues, ragged row counts, the 256 kernel alone (key 10 = 1) and as the 256 + 128 hybrid
-    (key 10 = 0; at M = 17 294 the QKV launch splits into two full rounds on the 256 kernel + 12 row panels on the 128
+    """Plain and LayerNorm-fold epilogues, ragged row counts, the 256 kernel alone (P256_MODE = 1) and as the 256 + 128 hybrid
+    (P256_MODE = 0; at M = 17 294 the QKV launch splits into two full rounds on the 256 kernel + 12 row panels on the 128
     kernel).  Odd M: the fold launches stay on the 128 kernel (the 256 kernel fetches the row statistics two rows per DMA
     element).  Repeated: a race in the 8-phase K loop would not necessarily show the first time."""
     for name, fn in _gemm_cases(M, dt).items():
-        tune(10, 2)
+        tune("P256_MODE", 2)
         ref = fn().clone()
         for mode in (1, 0):
-            tune(10, mode)
+            tune("P256_MODE", mode)
             for _ in range(3):
                 got = fn()
                 torch.cuda.synchronize()
@@ -92,11 +85,11 @@ def test_p256_inside_the_denoiser_with_device_side_row_counts(pc, tune, n_split)
         m.n_split = n_split
         args = [a.cuda() if torch.is_tensor(a) else a for a in pc.synth_inputs("SurfZNet", 512, 60, 1, False)]
         with torch.no_grad():
-            tune(10, 2)
+            tune("P256_MODE", 2)
             ref = m(*args).clone()
-            tune(10, 0)
+            tune("P256_MODE", 0)
             got = m(*args)
-            tune(10, 1)
+            tune("P256_MODE", 1)
             got1 = m(*args)
         assert torch.isfinite(ref).all() and torch.equal(ref, got) and torch.equal(ref, got1)
 

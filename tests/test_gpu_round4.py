@@ -7,6 +7,8 @@ import os
 import pytest
 import torch
 
+from gpu_check import tune  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 
 F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
@@ -34,17 +36,6 @@ def _record(key, value):
         json.dump(d, f, indent=1, sort_keys=True)
 
 
-@pytest.fixture
-def tune():
-    """bg_tune_set with automatic reset of the keys this file touches (8: phase-group delay, 10: 256-kernel mode, 12: split-kernel
-    choice, 13: fused QKV + attention, 15: small-launch threshold)."""
-    from brepgen_amd import _lib
-    lib = _lib.load()
-    yield lib.bg_tune_set
-    for k in (8, 10, 12, 13, 15):
-        lib.bg_tune_set(k, 0)
-
-
 def _split_case(M, K, dt, seed=0):
     g = torch.Generator().manual_seed(seed)
     rn = lambda *s: torch.randn(*s, generator=g)
@@ -60,8 +51,8 @@ def _split_case(M, K, dt, seed=0):
 @pytest.mark.parametrize("K", [768, 1024])
 @pytest.mark.parametrize("M", [1409, 128 * 11, 4999, 17294, 30720 + 78])
 def test_split_pipe_gemm_is_bit_identical(pc, tune, dt, K, M):
-    """out-proj (K = 768) and FFN2 (K = 1024) with split residual + row statistics: the pipelined kernel (key 12 = 0) against the
-    256 + 128 hybrid (key 12 = 1) and the 128 x 128 kernel alone (key 12 = 1, key 10 = 2): hi, lo and the statistics, out of place
+    """out-proj (K = 768) and FFN2 (K = 1024) with split residual + row statistics: the pipelined kernel (SPLIT_PIPE = 0) against the
+    256 + 128 hybrid (SPLIT_PIPE = 1) and the 128 x 128 kernel alone (SPLIT_PIPE = 1, P256_MODE = 2): hi, lo and the statistics, out of place
     and in place.  M covers one tile per workgroup (1409: 12 panels), many tiles per workgroup, ragged last panels.  Repeated: a race
     between the K loop and the epilogue it carries would not necessarily show the first time."""
     import hip_ops as ops
@@ -76,14 +67,14 @@ def test_split_pipe_gemm_is_bit_identical(pc, tune, dt, K, M):
         torch.cuda.synchronize()
         return r["out"].clone(), r["lo"].clone(), r["stats"].clone()
 
-    tune(15, -1)                                                  # (M = 1409 is 72 tiles: keep it off the small-launch path)
-    tune(12, 1)
-    tune(10, 2)
+    tune("SMALL_TILES", -1)                                                  # (M = 1409 is 72 tiles: keep it off the small-launch path)
+    tune("SPLIT_PIPE", 1)
+    tune("P256_MODE", 2)
     ref = run(False)
-    tune(10, 0)
+    tune("P256_MODE", 0)
     hyb = run(False)
     assert all(torch.equal(x, y) for x, y in zip(ref, hyb))
-    tune(12, 0)
+    tune("SPLIT_PIPE", 0)
     for rep in range(3):
         for inplace in (False, True):
             got = run(inplace)
@@ -101,9 +92,9 @@ def test_split_pipe_inside_the_denoiser_with_device_side_row_counts(pc, tune, n_
         m.n_split = n_split
         args = [a.cuda() if torch.is_tensor(a) else a for a in pc.synth_inputs("SurfZNet", 512, 60, 1, False)]
         with torch.no_grad():
-            tune(12, 1)
+            tune("SPLIT_PIPE", 1)
             ref = m(*args).clone()
-            tune(12, 0)
+            tune("SPLIT_PIPE", 0)
             for _ in range(2):
                 got = m(*args)
                 torch.cuda.synchronize()
@@ -115,9 +106,9 @@ def test_split_pipe_edge_net_shape_fp16(pc, tune):
     m, _ = pc.build_net("EdgeZNet", 9, False, F16, varlen=True)
     args = [a.cuda() if torch.is_tensor(a) else a for a in pc.synth_inputs("EdgeZNet", 8, 60, 40, False)]
     with torch.no_grad():
-        tune(12, 1)
+        tune("SPLIT_PIPE", 1)
         ref = m(*args).clone()
-        tune(12, 0)
+        tune("SPLIT_PIPE", 0)
         got = m(*args)
     assert torch.isfinite(ref).all() and torch.equal(ref, got)
 
@@ -126,7 +117,7 @@ def test_split_pipe_edge_net_shape_fp16(pc, tune):
 @pytest.mark.parametrize("M", [16 * 60, 960 + 37, 128])
 def test_small_launch_tiles_are_bit_identical(pc, tune, dt, M):
     """The reference's shipped batch (16 samples x 60 faces = 960 tokens): launches of < 160 tiles of 128 x 128 run on 64 x 64 tiles
-    (key 15 = -1 switches that off).  Every epilogue the encoder layers use -- plain, LayerNorm fold (+ ReLU), split residual +
+    (SMALL_TILES = -1 switches that off).  Every epilogue the encoder layers use -- plain, LayerNorm fold (+ ReLU), split residual +
     statistics -- must not depend on the tile shape: a sample's bits are the same at batch 16 and at batch 512."""
     import hip_ops as ops
     g = torch.Generator().manual_seed(3)
@@ -152,9 +143,9 @@ def test_small_launch_tiles_are_bit_identical(pc, tune, dt, M):
             return torch.cat([r["out"].float().flatten(), r["lo"].float().flatten(), r["stats"].flatten()])
         cases[name + " split"] = split
     for name, fn in cases.items():
-        tune(15, -1)
+        tune("SMALL_TILES", -1)
         ref = fn().clone()
-        tune(15, 0)
+        tune("SMALL_TILES", 0)
         for _ in range(2):
             got = fn()
             torch.cuda.synchronize()
@@ -162,17 +153,17 @@ def test_small_launch_tiles_are_bit_identical(pc, tune, dt, M):
 
 
 def test_p256_split_phase_groups_are_bit_identical(pc, tune):
-    """out-proj / FFN2 at the edge nets' row count on the 256 x 256 kernel alone (key 10 = 1), with the second phase group starting
-    late (key 8 = 24 x 1024 cycles, the default), much later (200) and not at all (-1): the delay moves when a tile is computed, never
+    """out-proj / FFN2 at the edge nets' row count on the 256 x 256 kernel alone (P256_MODE = 1), with the second phase group starting
+    late (GEMM_STAGGER: 24 x 1024 cycles, the default), much later (200) and not at all (-1): the delay moves when a tile is computed, never
     what it computes."""
     import hip_ops as ops
     for K in (768, 1024):
         a, w, b, hi, lo = _split_case(138752 + 5, K, BF16, seed=K)
         outs = []
         for mode, stag in ((2, 0), (1, -1), (1, 0), (1, 200), (0, 0)):
-            tune(12, 1 if mode == 2 else 0)
-            tune(10, mode)
-            tune(8, stag)
+            tune("SPLIT_PIPE", 1 if mode == 2 else 0)
+            tune("P256_MODE", mode)
+            tune("GEMM_STAGGER", stag)
             h, l = hi.clone(), lo.clone()
             r = ops.linear_ex(a, w, b, split_out=True, res=(h, l), want_stats=True, inplace=True)
             torch.cuda.synchronize()
@@ -252,9 +243,9 @@ def test_fused_qkv_attention_inside_the_densely_executed_masked_net(pc, tune, n_
     m.n_split = n_split
     args = [a.cuda() if torch.is_tensor(a) else a for a in pc.synth_inputs("SurfZNet", 512, 60, 1, False)]
     with torch.no_grad():
-        tune(13, 1)
+        tune("QKV_ATTN", 1)
         ref = m(*args).clone()
-        tune(13, 0)
+        tune("QKV_ATTN", 0)
         for _ in range(2):
             got = m(*args)
             torch.cuda.synchronize()
@@ -264,15 +255,15 @@ def test_fused_qkv_attention_inside_the_densely_executed_masked_net(pc, tune, n_
 @pytest.mark.parametrize("dt", [BF16, F16])
 @pytest.mark.parametrize("B,S,n_split", [(512, 60, 1), (512, 60, 2), (512, 30, 1), (300, 60, 2)])
 def test_fused_qkv_attention_inside_the_denoiser(pc, tune, dt, B, S, n_split):
-    """SurfPosNet at the face LDM's shapes: eps with the fused launch == eps with GEMM + attention (key 13 = 1), bit for bit,
+    """SurfPosNet at the face LDM's shapes: eps with the fused launch == eps with GEMM + attention (QKV_ATTN = 1), bit for bit,
     one and two sample groups in flight."""
     m, _ = pc.build_net("SurfPosNet", 11, False, dt)
     m.n_split = n_split
     args = [a.cuda() if torch.is_tensor(a) else a for a in pc.synth_inputs("SurfPosNet", B, S, 1, False)]
     with torch.no_grad():
-        tune(13, 1)
+        tune("QKV_ATTN", 1)
         ref = m(*args).clone()
-        tune(13, 0)
+        tune("QKV_ATTN", 0)
         for _ in range(2):
             got = m(*args)
             torch.cuda.synchronize()
@@ -411,14 +402,14 @@ def test_fused_qkv_attention_on_a_slot_packed_ragged_batch(pc, dt, B, N, lo):
 @pytest.mark.parametrize("dt", [BF16, F16])
 def test_slot_packed_execution_inside_the_denoiser(pc, tune, dt, n_split):
     """SurfZNet at the headline shape (512 x 60, ragged mask), variable-length execution: slot-packed rows + the fused launch against
-    the dense packing + GEMM + attention (key 13 = 1): eps bit for bit, zeros at the padded positions."""
+    the dense packing + GEMM + attention (QKV_ATTN = 1): eps bit for bit, zeros at the padded positions."""
     m, _ = pc.build_net("SurfZNet", 5, False, dt, varlen=True)
     m.n_split = n_split
     args = [a.cuda() if torch.is_tensor(a) else a for a in pc.synth_inputs("SurfZNet", 512, 60, 1, False)]
     with torch.no_grad():
-        tune(13, 1)
+        tune("QKV_ATTN", 1)
         ref = m(*args).clone()
-        tune(13, 0)
+        tune("QKV_ATTN", 0)
         for _ in range(2):
             got = m(*args)
             torch.cuda.synchronize()

@@ -8,6 +8,8 @@ import os
 import pytest
 import torch
 
+from gpu_check import tune  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 
 F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
@@ -104,19 +106,10 @@ def test_time_table_equals_per_call_time_mlp(pc, dt):
 
 
 # ---- qkv_attn.hip: the XCD-pinned tile walk -----------------------------------------------------------------------------------
-@pytest.fixture
-def tune():
-    from brepgen_amd import _lib
-    lib = _lib.load()
-    yield lib.bg_tune_set
-    for k in (12, 13, 14):
-        lib.bg_tune_set(k, 0)
-
-
 @pytest.mark.parametrize("dt", [BF16, F16])
 @pytest.mark.parametrize("B,N", [(512, 60), (300, 48), (37, 60), (130, 30), (8, 60), (67, 64)])
 def test_qkv_attn_pinned_walk_is_bit_identical(pc, tune, dt, B, N):
-    """bg_tune key 14: 1 = plain walk, 2 = XCD-pinned head halves wherever the grid allows (a different ORDER of the same tiles)."""
+    """QKV_WALK: 1 = plain walk, 2 = XCD-pinned head halves wherever the grid allows (a different ORDER of the same tiles)."""
     import hip_ops as ops
     g = torch.Generator().manual_seed(B * 7 + N)
     M = B * N
@@ -129,7 +122,7 @@ def test_qkv_attn_pinned_walk_is_bit_identical(pc, tune, dt, B, N):
     a = x.to(dt).cuda()
     outs = []
     for walk in (1, 2, 0):
-        tune(14, walk)
+        tune("QKV_WALK", walk)
         outs.append(ops.qkv_attention(a, w, b, cs, stats, B, N))
     torch.cuda.synchronize()
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
@@ -147,7 +140,7 @@ def test_pinned_walk_inside_the_denoisers(pc, tune, ns):
         res = []
         with torch.no_grad():
             for walk in (1, 2, 0):
-                tune(14, walk)
+                tune("QKV_WALK", walk)
                 res.append(m(*cu))
         torch.cuda.synchronize()
         assert torch.equal(res[0], res[1]) and torch.equal(res[0], res[2]), net

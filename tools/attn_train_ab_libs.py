@@ -13,7 +13,6 @@ training attention entries bg_attn_train_fwd / bg_attn_bwd of both on the same s
 Every step (the bit cases, each timed shape) runs under its own alarm; nothing is retried.  Exit status 1 on a byte mismatch, 2 on a
 shape outside its margin.     python tools/attn_train_ab_libs.py [--out profiles/r14/attn_tile_ab.json]"""
 import argparse
-import ctypes as C
 import json
 import os
 import signal
@@ -25,6 +24,7 @@ sys.path.insert(0, ROOT)
 import torch
 
 from brepgen_amd import _lib
+from bench_common import old_library
 
 ENTRIES = ("bg_attn_train_fwd", "bg_attn_bwd", "bg_attn_bwd_workspace_bytes")
 DT = {torch.float16: _lib.BG_F16, torch.bfloat16: _lib.BG_BF16}
@@ -32,14 +32,6 @@ GENERAL, SHORT, AUTO = _lib.BG_ATTN_BWD_GENERAL, _lib.BG_ATTN_BWD_SHORT, _lib.BG
 BIT_SHAPES = ((3, 5), (3, 33), (3, 64), (2, 130))
 TIME_SHAPES = ((512, 30), (512, 50), (512, 64), (64, 1500))
 SEED, DRAW = 0x5EED, 3
-
-
-def load_old():
-    old = C.CDLL(os.path.join(ROOT, "brepgen_amd", "_ab_old.so"))
-    for name in ENTRIES:
-        fn = getattr(old, name)
-        fn.restype, fn.argtypes = _lib._SIGNATURES[name]
-    return old
 
 
 def operands(B, N, dtype, mask, seed):
@@ -179,7 +171,7 @@ def main():
     args = ap.parse_args()
     with open(args.isa) as f:
         isa = json.load(f)["kernels"]
-    new, old = _lib.load(), load_old()
+    new, old = _lib.load(), old_library(_lib._SIGNATURES, ENTRIES)
     res = {"device": torch.cuda.get_device_name(0), "min_calls_per_window": args.iters, "min_window_us": args.window_us, "rounds": args.rounds}
     signal.alarm(args.step_timeout)
     res["bits"] = bit_cases(old, new)

@@ -1,4 +1,4 @@
-"""What the bench tools share: the median, the two alternated device-event timers, the device's state, the parent loop that runs
+"""What the bench tools share: the median, the two alternated device-event timers, the old build of a two-library A/B, the device's state, the parent loop that runs
 one time-limited child process per shape, and the command line of the training benches around it.  Imports neither torch nor the
 package: the parent of a bench never touches the device."""
 import argparse
@@ -46,6 +46,17 @@ def phases(torch, fns, iters, rounds, warmup, n=1, all_rounds=False):
             for p in range(n):
                 ms[name][p].append(sum(e[p].elapsed_time(e[p + 1]) for e in evs) / iters)
     return ms if all_rounds else {k: [med(v) for v in per] for k, per in ms.items()}
+
+
+def old_library(signatures, entries):
+    """The two-library A/B tools' second library: brepgen_amd/_ab_old.so (the previous commit's build, copied there by hand) with the
+    signatures of `entries` taken from `signatures` (the binding's table, brepgen_amd/_lib.py _SIGNATURES)."""
+    import ctypes
+    old = ctypes.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "brepgen_amd", "_ab_old.so"))
+    for name in entries:
+        fn = getattr(old, name)
+        fn.restype, fn.argtypes = signatures[name]
+    return old
 
 
 def device_state(torch):

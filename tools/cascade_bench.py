@@ -26,9 +26,7 @@ def run(B=256, datalike=False, graphs=False):
     nets = [cls(False).to(dev).eval() for cls in (bga.SurfPosNet, bga.SurfZNet, bga.EdgePosNet, bga.EdgeZNet)]
     if os.environ.get("BG_SURFZ_VARLEN") in ("0", "1"):             # experiments: force SurfZNet's variable-length execution on / off
         nets[1].varlen = os.environ["BG_SURFZ_VARLEN"] == "1"
-    for kv in filter(None, os.environ.get("BG_TUNE", "").split(",")):   # experiments: bg_tune_set key=value[,key=value]
-        from brepgen_amd import _lib
-        _lib.load().bg_tune_set(int(kv.split("=")[0]), int(kv.split("=")[1]))
+    # (experiments with the kernel-selection knobs: BG_TUNE="P256_MODE=2,13=1" in the environment -- brepgen_amd/_lib.py applies it at load)
     surf_vae = bga.AutoencoderKLFastDecode(**SURF_VAE_CFG).to(dev).eval()
     edge_vae = bga.AutoencoderKL1DFastDecode(**EDGE_VAE_CFG).to(dev).eval()
     surf_vae.compute_dtype = edge_vae.compute_dtype = torch.bfloat16

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """In-process A/B of bg_tune settings on the three face-LDM loops of bench.py (one box, one process, interleaved rounds):
-    python tools/face_ldm_ab.py "10=2" "10=0" ...        each argument = one setting (key=value,...); BG_SPLITS=1,2,4: the n_split values
-A key that is not a number names an attribute of the two drop-in modules instead (e.g. "fuse_output=0,time_table_steps=0")."""
+    python tools/face_ldm_ab.py "P256_MODE=2" "10=0" ... each argument = one setting (key=value,...); BG_SPLITS=1,2,4: the n_split values
+A key that is neither a knob's name nor a number names an attribute of the two drop-in modules instead (e.g. "fuse_output=0,time_table_steps=0")."""
 import os
 import statistics
 import sys
@@ -15,28 +15,26 @@ import bench
 from brepgen_amd import _lib
 
 SETTINGS = sys.argv[1:] or ["10=2", "10=0"]
-KEYS = sorted({int(kv.split("=")[0]) for s in SETTINGS for kv in s.split(",") if kv and kv.split("=")[0].isdigit()})
-ATTRS = sorted({kv.split("=")[0] for s in SETTINGS for kv in s.split(",") if kv and not kv.split("=")[0].isdigit()})
-lib = _lib.load()
 dev = torch.device("cuda")
 ldm = bench.FaceLDM(dev, 0)
 STEPS, ROUNDS = 20, 3
+
+
+def split_setting(setting):
+    """({Tune: value}, {module attribute: value}) of one setting"""
+    pairs = [kv.split("=") for kv in filter(None, setting.split(","))]
+    knob = lambda k: k.isdigit() or k in _lib.Tune.__members__
+    return _lib.parse_tune(",".join(f"{k}={v}" for k, v in pairs if knob(k))), {k: int(v) for k, v in pairs if not knob(k)}
+
+
+ATTRS = sorted({a for s in SETTINGS for a in split_setting(s)[1]})
 DEFAULTS = {a: getattr(ldm.pos_net, a) for a in ATTRS}
 
 
-def apply(setting):
-    for k in KEYS:
-        lib.bg_tune_set(k, 0)
+def set_attrs(attrs):
     for a, d in DEFAULTS.items():
         for net in (ldm.pos_net, ldm.z_net):
-            setattr(net, a, d)
-    for kv in filter(None, setting.split(",")):
-        k, v = kv.split("=")
-        if k.isdigit():
-            lib.bg_tune_set(int(k), int(v))
-        else:
-            for net in (ldm.pos_net, ldm.z_net):
-                setattr(net, k, type(DEFAULTS[k])(int(v)))
+            setattr(net, a, type(d)(attrs.get(a, d)))
 
 
 def clock(ks):
@@ -53,12 +51,14 @@ for split in [int(v) for v in os.environ.get("BG_SPLITS", "1,2").split(",")]:
     res = {(s, leg): [] for s in SETTINGS for leg in "ABC"}
     for r in range(ROUNDS):
         for s in SETTINGS:
-            apply(s)
-            for leg, ks in zip("ABC", ((STEPS, 0, 0), (0, STEPS, 0), (0, 0, STEPS))):
-                res[(s, leg)].append(clock(ks))
+            knobs, attrs = split_setting(s)
+            set_attrs(attrs)
+            with _lib.tune(knobs):
+                for leg, ks in zip("ABC", ((STEPS, 0, 0), (0, STEPS, 0), (0, 0, STEPS))):
+                    res[(s, leg)].append(clock(ks))
     print(f"n_split = {split}   (ms per step, median of {ROUNDS} rounds x {STEPS} steps; composite = (158 A + 250 B + 209 C) / 617)")
     for s in SETTINGS:
         m = {leg: statistics.median(res[(s, leg)]) for leg in "ABC"}
         comp = (158 * m["A"] + 250 * m["B"] + 209 * m["C"]) / 617
         print(f"  {s:24s} A {m['A']:.3f}  B {m['B']:.3f}  C {m['C']:.3f}  composite {comp:.3f}")
-apply("")
+set_attrs({})

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The 256 x 256 persistent 8-phase GEMM (csrc/gemm_p256.hip) against the 128 x 128 persistent kernel: bit-equality of the
 plain / LayerNorm-fold epilogues on ragged row counts (bf16 and fp16), then interleaved timings on the per-layer shapes and on
-square problems.   python tools/gemm_p256_check.py [M ...]      (bg_tune key 10: 0 = the 256 + 128 hybrid the library picks,
+square problems.   python tools/gemm_p256_check.py [M ...]      (P256_MODE: 0 = the 256 + 128 hybrid the library picks,
 1 = force the 256 kernel, 2 = never)"""
 import os
 import statistics
@@ -15,14 +15,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import hip_ops as ops
 
 MS = [int(v) for v in sys.argv[1:]] or [8640, 17280, 30720, 61440, 138752]
-lib = _lib.load()
 dev = "cuda"
 g = torch.Generator().manual_seed(0)
 rn = lambda *s: torch.randn(*s, generator=g)
-
-
-def setv(mode):
-    lib.bg_tune_set(10, mode)
 
 
 TIMING = False
@@ -72,15 +67,15 @@ bad = 0
 for dt in (torch.bfloat16, torch.float16):
     for M in (1037, 1038, 256 * 7, 4999, 17294, 30720 + 78):
         for k, (fn, N, K) in build(M, dt).items():
-            lib.bg_tune_set(10, 2)
-            ref = fn().clone()
+            with _lib.tune(P256_MODE=2):
+                ref = fn().clone()
             res = []
             for mode in (1, 0):
-                setv(mode)
-                for rep in range(3):                                  # repeated: a race would not necessarily show the first time
-                    got = fn()
-                    torch.cuda.synchronize()
-                    res.append(torch.equal(ref, got))
+                with _lib.tune(P256_MODE=mode):
+                    for rep in range(3):                              # repeated: a race would not necessarily show the first time
+                        got = fn()
+                        torch.cuda.synchronize()
+                        res.append(torch.equal(ref, got))
             ok = all(res)
             bad += not ok
             if not ok or M == 1038:
@@ -93,14 +88,14 @@ for M in MS:
     cases = build(M, dt)
     res = {(k, v[0]): [] for k in cases for v in VARS}
     for r in range(5):
-        for name, *kv in VARS:
-            setv(*kv)
-            for k, (fn, N, K) in cases.items():
-                res[(k, name)].append(timed(fn))
+        for name, mode in VARS:
+            with _lib.tune(P256_MODE=mode):
+                for k, (fn, N, K) in cases.items():
+                    res[(k, name)].append(timed(fn))
     print(f"M = {M}")
     for k, (fn, N, K) in cases.items():
         line = f"  {k:12s}"
-        for name, *kv in VARS:
+        for name, _ in VARS:
             us = statistics.median(res[(k, name)])
             line += f" | {name} {us:6.1f} {2.0 * M * N * K / us / 1e6:4.0f}"
         print(line)
@@ -110,9 +105,8 @@ for S in (4096, 8192):
     b = rn(S).to(dev)
     fn = lambda: ops.linear(a, w, b, out_dtype=dt)
     line = f"square {S}^3 plain:"
-    for name, *kv in VARS:
-        setv(*kv)
-        us = statistics.median(timed(fn, 10) for _ in range(3))
+    for name, mode in VARS:
+        with _lib.tune(P256_MODE=mode):
+            us = statistics.median(timed(fn, 10) for _ in range(3))
         line += f" | {name} {us:7.1f} {2.0 * S * S * S / us / 1e6:4.0f}"
     print(line)
-setv(0)

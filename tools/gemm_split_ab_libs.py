@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Two builds of libbrepgen_hip.so in ONE process (brepgen_amd/_ab_old.so = the previous commit's build, copied there by hand): the
-residual-stream GEMMs (bg_gemm_ex_fwd, split residual in place + statistics) on the 256 x 256 kernel alone (bg_tune key 10 = 1) and as the
+residual-stream GEMMs (bg_gemm_ex_fwd, split residual in place + statistics) on the 256 x 256 kernel alone (P256_MODE = 1) and as the
 library picks, bit-equality and interleaved timings.     python tools/gemm_split_ab_libs.py [M ...]"""
 import ctypes as C
 import os
@@ -12,11 +12,11 @@ sys.path.insert(0, ROOT)
 import torch
 
 from brepgen_amd import _lib
+from bench_common import old_library
 
 new = _lib.load()
-old = C.CDLL(os.path.join(ROOT, "brepgen_amd", "_ab_old.so"))
-old.bg_gemm_ex_fwd.restype, old.bg_gemm_ex_fwd.argtypes = _lib._SIGNATURES["bg_gemm_ex_fwd"]
-old.bg_tune_set.restype, old.bg_tune_set.argtypes = C.c_int, [C.c_int, C.c_int]
+old = old_library(_lib._SIGNATURES, ("bg_gemm_ex_fwd", "bg_tune_set"))
+P256_MODE = int(_lib.Tune.P256_MODE)                # (the old build's knob is set directly: _lib.tune holds the package's library only)
 MS = [int(v) for v in sys.argv[1:]] or [18432, 30720, 61440, 138752]
 dt = torch.bfloat16
 st = torch.cuda.current_stream().cuda_stream
@@ -56,29 +56,28 @@ def timed(fn, n=20):
 
 
 for mode in (1, 0):
-    for lib in (old, new):
-        lib.bg_tune_set(10, mode)
-    print("256 x 256 kernel alone (key 10 = 1)" if mode else "library default", flush=True)
-    for M in MS:
-        for name, K in (("outproj", 768), ("ffn2", 1024)):
-            a, w, b, hi, lo = case(M, K, seed=M + K)
-            outs = []
-            for lib in (old, new):
+    old.bg_tune_set(P256_MODE, mode)
+    with _lib.tune(P256_MODE=mode):
+        print("256 x 256 kernel alone (P256_MODE = 1)" if mode else "library default", flush=True)
+        for M in MS:
+            for name, K in (("outproj", 768), ("ffn2", 1024)):
+                a, w, b, hi, lo = case(M, K, seed=M + K)
+                outs = []
+                for lib in (old, new):
+                    h, l = hi.clone(), lo.clone()
+                    stats = torch.zeros(12, M, 2, device="cuda")
+                    d = desc(a, w, b, h, l, stats, M, K)
+                    assert lib.bg_gemm_ex_fwd(C.byref(d), st) == 0
+                    torch.cuda.synchronize()
+                    outs.append((h, l, stats))
+                same = all(torch.equal(x, y) for x, y in zip(*outs))
                 h, l = hi.clone(), lo.clone()
                 stats = torch.zeros(12, M, 2, device="cuda")
                 d = desc(a, w, b, h, l, stats, M, K)
-                assert lib.bg_gemm_ex_fwd(C.byref(d), st) == 0
-                torch.cuda.synchronize()
-                outs.append((h, l, stats))
-            same = all(torch.equal(x, y) for x, y in zip(*outs))
-            h, l = hi.clone(), lo.clone()
-            stats = torch.zeros(12, M, 2, device="cuda")
-            d = desc(a, w, b, h, l, stats, M, K)
-            res = {"old": [], "new": []}
-            for r in range(5):
-                for nm, lib in (("old", old), ("new", new)):
-                    res[nm].append(timed(lambda: lib.bg_gemm_ex_fwd(C.byref(d), st)))
-            to, tn = statistics.median(res["old"]), statistics.median(res["new"])
-            print(f"  M={M:6d} {name:8s} {'bit-identical' if same else 'MISMATCH'}   old {to:7.1f} us   new {tn:7.1f} us   ({tn / to:.3f})", flush=True)
-for lib in (old, new):
-    lib.bg_tune_set(10, 0)
+                res = {"old": [], "new": []}
+                for r in range(5):
+                    for nm, lib in (("old", old), ("new", new)):
+                        res[nm].append(timed(lambda: lib.bg_gemm_ex_fwd(C.byref(d), st)))
+                to, tn = statistics.median(res["old"]), statistics.median(res["new"])
+                print(f"  M={M:6d} {name:8s} {'bit-identical' if same else 'MISMATCH'}   old {to:7.1f} us   new {tn:7.1f} us   ({tn / to:.3f})", flush=True)
+old.bg_tune_set(P256_MODE, 0)

@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """Two builds of libbrepgen_hip.so in ONE process (brepgen_amd/_ab_old.so = the previous commit's build, copied there by hand): the fused
 QKV + attention launch of both, bit-equality and interleaved timings.     python tools/qkv_attn_ab_libs.py"""
-import ctypes as C
 import os
 import statistics
 import sys
@@ -11,13 +10,10 @@ sys.path.insert(0, ROOT)
 import torch
 
 from brepgen_amd import _lib
+from bench_common import old_library
 
 new = _lib.load()
-old = C.CDLL(os.path.join(ROOT, "brepgen_amd", "_ab_old.so"))
-for lib in (old,):
-    res, args = _lib._SIGNATURES["bg_qkv_attn_fwd"]
-    lib.bg_qkv_attn_fwd.restype, lib.bg_qkv_attn_fwd.argtypes = res, args
-    lib.bg_tune_set.restype, lib.bg_tune_set.argtypes = C.c_int, [C.c_int, C.c_int]
+old = old_library(_lib._SIGNATURES, ("bg_qkv_attn_fwd",))
 dt = torch.bfloat16
 st = torch.cuda.current_stream().cuda_stream
 
