@@ -16,8 +16,9 @@ Drop-in for the reference's call surface on that path only:
     nn.LayerNorm, ReLU, nn.Dropout and the residual adds of the encoder layers in net.train() (layer.py) -> bg_ln_train_fwd / bg_ln_bwd / bg_dropout_add_fwd / bg_relu_dropout_fwd
     the denoisers' embed MLPs / time_embed / fc_out and the masked-MSE loss in training (mlp.py, training.mse_loss) -> bg_thin_expand / bg_thin_contract / bg_thin_wgrad / bg_ln_silu_train_fwd / bg_ln_silu_bwd / bg_masked_mse_bwd
     the VAEs' ResnetBlock2D in training: GroupNorm + SiLU + 3x3 conv forward, dX, dW + db, GroupNorm backward (conv.py) -> bg_conv_wgrad / bg_conv_weight_pack / bg_gn_act_bwd + the VAE forward entries
-      (not built: the rest of the VAE backward -- up-sampling / stride-2 convolutions, conv_in / conv_out, mid-block attention, the 1-D
-      blocks and resamplers, the posterior, a whole-VAE training step)
+    the VAEs' Downsample2D / Upsample2D convolutions in training, and whole down / up blocks (conv.py) -> bg_conv_wgrad_geom / bg_conv_down_dgrad / bg_conv_weight_pack_down / bg_pool2x2_sum
+      (not built: the rest of the VAE backward -- conv_in / conv_out, mid-block attention, the 1-D blocks and resamplers, the
+      posterior, a whole-VAE training step)
 All compute goes through libbrepgen_hip.so (hand-written HIP kernels behind a C ABI, include/brepgen_hip.h).
 """
 from . import optim  # noqa: F401
@@ -62,7 +63,8 @@ _MLP = ("thin_linear_in", "thin_linear_out", "ln_silu", "DeviceMLP", "use_device
 _TRAINING = ("mse_loss", "use_device_training")
 __all__ += list(_MLP + _TRAINING)
 # the VAEs' ResnetBlock2D in training: GroupNorm + activation + convolution, forward and backward on the device (conv.py)
-_CONV = ("gn_act_conv", "DeviceResnetBlock2D", "use_device_resnets")
+_CONV = ("gn_act_conv", "DeviceResnetBlock2D", "use_device_resnets", "conv_down", "conv_up", "DeviceDownsample2D", "DeviceUpsample2D",
+         "DeviceBlock2D", "use_device_blocks")
 __all__ += list(_CONV)
 
 

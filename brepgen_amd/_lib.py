@@ -16,6 +16,7 @@ BG_ACT_NONE, BG_ACT_RELU = 0, 1
 BG_SURFPOS, BG_SURFZ, BG_EDGEPOS, BG_EDGEZ = 0, 1, 2, 3
 BG_MAX_LAYERS, BG_MAX_EMBEDS = 12, 5
 BG_ATTN_BWD_AUTO, BG_ATTN_BWD_GENERAL, BG_ATTN_BWD_SHORT = 0, 1, 2      # enum bg_attn_bwd_variant
+BG_CONV_SAME, BG_CONV_DOWN2, BG_CONV_UP2 = 0, 1, 2                      # enum bg_conv_geom
 
 vp, fp, i64p, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # device pointers travel as integers
 
@@ -222,6 +223,13 @@ _SIGNATURES = {
     "bg_conv_weight_pack": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "bg_gn_act_bwd_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "bg_gn_act_bwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]),
+    "bg_conv_wgrad_geom": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp] + [C.c_int] * 11 + [vp, C.c_size_t, vp]),
+    "bg_conv_wgrad_geom_workspace_bytes": (C.c_size_t, [C.c_int] * 9),
+    "bg_conv_wgrad_geom_split": (C.c_int, [C.c_int] * 8),
+    "bg_conv_weight_pack_down": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "bg_conv_down_dgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "bg_conv_down_dgrad": (C.c_int, [vp, C.c_int, vp, fp] + [C.c_int] * 6 + [vp, C.c_size_t, vp]),
+    "bg_pool2x2_sum": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -6,6 +6,12 @@ bg_conv_gemm_fwd / bg_gemm_bias_act_fwd) for the forward and the data gradient.
     DeviceResnetBlock2D(cin, cout, groups=32, eps=1e-6) diffusers' ResnetBlock2D (no time embedding, dropout 0, output scale 1) with its
                                                         parameter names; forward and backward as ONE autograd node
     use_device_resnets(module)                          swaps it in for every child with exactly that parameter structure
+    conv_down(x, conv) / conv_up(x, conv)               diffusers' Downsample2D / Upsample2D convolutions (pad after + stride 2 | nearest x2 +
+                                                        'same'), torch.autograd.Functions: bg_conv_wgrad_geom, bg_conv_down_dgrad /
+                                                        bg_conv_weight_pack_down, bg_pool2x2_sum for the backward
+    DeviceDownsample2D(c) / DeviceUpsample2D(c)         the two modules, parameter name `conv`
+    DeviceBlock2D(resnets, downsamplers, upsamplers)    a DownEncoderBlock2D / UpDecoderBlock2D: the resnets, then the sampler
+    use_device_blocks(module)                           use_device_resnets + the samplers + the blocks around them
 
 Layout.  Everything here takes and returns CHANNELS-LAST fp32 activations: a dense [S, H, W, C] tensor (1-D: [S, L, C]), which is
 `x.permute(0, 2, 3, 1).contiguous()` of torch's [S, C, H, W] -- not a torch memory format of a 4-D NCHW tensor.  A module converted by
@@ -16,8 +22,10 @@ weights are cast per call by one launch (bg_conv_weight_pack), products accumula
 gradients in fp32 straight from the fp32 sums.  Calls outside autocast, CPU tensors, strides other than 1, grids that are no powers
 of two and channel counts the kernels do not take raise; nothing falls back to torch.
 
-Not here (the rest of the VAE backward): the up-sampling and stride-2 convolutions, conv_in / conv_out, the mid-block attention, the
-1-D ResConvBlock composition and cubic resamplers, the posterior's backward, a whole-VAE training step.
+Not here (the rest of the VAE backward): conv_in / conv_out, the mid-block attention, the 1-D ResConvBlock composition and cubic
+resamplers, the posterior's backward, a whole-VAE training step.  Nor is nearest x2 + 3x3 folded into four 2x2 class convolutions
+with summed weights (16 instead of 36 tap-products per low-resolution pixel): that changes the rounding of a forward that inference
+and the goldens share.
 """
 import torch
 import torch.nn as nn
@@ -364,3 +372,280 @@ def use_device_resnets(module):
         else:
             use_device_resnets(child)
     return module
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Downsample2D / Upsample2D: the two 3x3 resampling convolutions, and whole down / up blocks
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _gemm(lib, col, K, w16, bias, M, N, dt):
+    out = torch.empty(M, N, dtype=torch.float32, device=col.device)
+    _lib.check(lib.bg_gemm_bias_act_fwd(_lib.ptr(col), K, _lib.ptr(w16), _lib.ptr(bias), _lib.ptr(out), N, M, N, N, K, DTYPES[dt], _lib.BG_F32,
+                                        _lib.BG_ACT_NONE, None, 0, 1, _lib.stream()), "bg_gemm_bias_act_fwd")
+    return out
+
+
+def _gather(lib, x, S, H, W, C, dt, up, stride, pad, Ho, Wo):
+    """the im2col matrix [S*Ho*Wo, 9C] of a 3x3 window over x fp32 [S, H, W, C], rounded to dt: bg_im2col's `up`, `stride` and before-padding"""
+    col = torch.empty(S * Ho * Wo, 9 * C, dtype=dt, device=x.device)
+    _lib.check(lib.bg_im2col(_lib.ptr(x), _lib.ptr(col), DTYPES[dt], S, H, W, C, 3, 3, up, stride, pad, pad, Ho, Wo, None, None, None, 1, 0, None,
+                             _lib.stream()), "bg_im2col")
+    return col
+
+
+def _wgrad_geom(lib, dy16, a, weight, S, H, W, geom, dt, need_w, need_b):
+    """(dw in the parameter's [N, C, 3, 3] layout, db) of a resampling convolution; H x W: the grid of the 16-bit a [S*H*W, C]"""
+    N, C = weight.shape[:2]
+    dwp, db = weight_grad(weight, dt, (N, 9 * C), need_w, need_b, lib.bg_conv_wgrad_geom_workspace_bytes(S, H, W, N, C, 3, 3, geom, 0),
+                          lambda dwp, db, odt, ws, nbytes: _lib.check(lib.bg_conv_wgrad_geom(
+                              _lib.ptr(dy16), N, _lib.ptr(a), C, _lib.ptr(dwp), _lib.ptr(db), S, H, W, N, C, 3, 3, geom, DTYPES[dt], odt, 0,
+                              _lib.ptr(ws), nbytes, _lib.stream()), "bg_conv_wgrad_geom"))
+    return (dwp.view(N, 3, 3, C).permute(0, 3, 1, 2).contiguous() if need_w else None), db
+
+
+def _pack_down(lib, weight, dt):
+    """the class-ordered pack of bg_conv_down_dgrad (9*C*N elements) of a conv weight [N, C, 3, 3]"""
+    N, C = weight.shape[:2]
+    w = weight.detach().contiguous()
+    out = torch.empty(9 * C * N, dtype=dt, device=w.device)
+    _lib.check(lib.bg_conv_weight_pack_down(_lib.ptr(w), DTYPES[w.dtype], N, C, None, _lib.ptr(out), DTYPES[dt], _lib.stream()),
+               "bg_conv_weight_pack_down")
+    return out
+
+
+def _down_dgrad(lib, dy16, pack, S, H, W, N, C, dt):
+    """dx fp32 [S, H, W, C] of the stride-2 convolution from dy16 [S*H/2*W/2, N]"""
+    dx = torch.empty(S, H, W, C, dtype=torch.float32, device=dy16.device)
+    nbytes = lib.bg_conv_down_dgrad_workspace_bytes(S, H, W, N, C)
+    ws = workspace(nbytes, dy16.device)
+    _lib.check(lib.bg_conv_down_dgrad(_lib.ptr(dy16), N, _lib.ptr(pack), _lib.ptr(dx), S, H, W, N, C, DTYPES[dt], _lib.ptr(ws), nbytes,
+                                      _lib.stream()), "bg_conv_down_dgrad")
+    return dx
+
+
+def _pool2x2(lib, u, S, H, W, C, add=None):
+    """y fp32 [S, H, W, C]: the 2 x 2 sums of u [S*2H*2W, C] (+ add)"""
+    y = torch.empty(S, H, W, C, dtype=torch.float32, device=u.device)
+    _lib.check(lib.bg_pool2x2_sum(_lib.ptr(u), _lib.ptr(add), _lib.ptr(y), S, H, W, C, _lib.stream()), "bg_pool2x2_sum")
+    return y
+
+
+def _up_fwd(lib, x, a, S, H, W, C, w16, N, bias, dt):
+    """conv 3x3 'same' on the nearest-x2 grid of x [S, H, W, C] -> fp32 [S*2H*2W, N]: the implicit GEMM (up = 1) on the 16-bit a where its
+    64-tile rule holds, else im2col (up = 1) from x + GEMM -- vae_exec.hip's choice"""
+    Ho, Wo = 2 * H, 2 * W
+    if not _implicit_ok(S, Ho, Wo, C, N, 9):
+        return _gemm(lib, _gather(lib, x, S, H, W, C, dt, 1, 1, 1, Ho, Wo), 9 * C, w16, bias, S * Ho * Wo, N, dt)
+    out = torch.empty(S * Ho * Wo, N, dtype=torch.float32, device=a.device)
+    d = _lib.ConvDesc()
+    d.x, d.S, d.H, d.W, d.C = _lib.ptr(a), S, H, W, C
+    d.kh, d.kw, d.up = 3, 3, 1
+    d.w, d.bias, d.N = _lib.ptr(w16), _lib.ptr(bias), N
+    d.out, d.ldc = _lib.ptr(out), N
+    d.add, d.ld_add = None, N
+    d.dtype, d.zero_page = DTYPES[dt], _lib.ptr(_zero_page(a.device))
+    _lib.check(lib.bg_conv_gemm_fwd(d, _lib.stream()), "bg_conv_gemm_fwd")
+    return out
+
+
+class _Resample(torch.autograd.Function):
+    """conv_down (down=True) / conv_up: keeps the 16-bit cast of x -- for conv_up the LOW-resolution one -- and the parameters"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, down, dt):
+        S, H, W, C = x.shape
+        N = weight.shape[0]
+        with torch.autocast(device_type="cuda", enabled=False):
+            lib = _lib.load()
+            x = x.contiguous()
+            a = _norm_act_cast(lib, x, S, H, W, C, dt)
+            w16 = _pack(lib, weight, 3, 3, dt, True)
+            b32 = None if bias is None else fp32(bias)
+            if down:
+                Ho, Wo = H // 2, W // 2
+                y = _gemm(lib, _gather(lib, x, S, H, W, C, dt, 0, 2, 0, Ho, Wo), 9 * C, w16, b32, S * Ho * Wo, N, dt)
+            else:
+                Ho, Wo = 2 * H, 2 * W
+                y = _up_fwd(lib, x, a, S, H, W, C, w16, N, b32, dt)
+        ctx.a, ctx.params, ctx.geo = a, (weight, bias), (S, H, W, C, N, Ho, Wo, down, dt)
+        return y.view(S, Ho, Wo, N)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        S, H, W, C, N, Ho, Wo, down, dt = ctx.geo
+        weight, bias = ctx.params
+        need = ctx.needs_input_grad
+        need_b = bias is not None and need[2]
+        dx = dw = db = None
+        with torch.autocast(device_type="cuda", enabled=False):
+            lib = _lib.load()
+            dy = dy.float().contiguous()
+            dy16 = _norm_act_cast(lib, dy, S, Ho, Wo, N, dt)
+            if need[1] or need_b:
+                dw, db = _wgrad_geom(lib, dy16, ctx.a, weight, S, H, W, _lib.BG_CONV_DOWN2 if down else _lib.BG_CONV_UP2, dt, need[1], need_b)
+            if need[0] and down:
+                dx = _down_dgrad(lib, dy16, _pack_down(lib, weight, dt), S, H, W, N, C, dt)
+            elif need[0]:
+                da_up = _conv_same(lib, dy, dy16, S, Ho, Wo, N, 3, 3, _pack(lib, weight, 3, 3, dt, False), C, None, None)
+                dx = _pool2x2(lib, da_up, S, H, W, C)
+        return dx, grad_as(dw, weight.dtype), grad_as(db, bias.dtype) if bias is not None else None, None, None
+
+
+def _check_resample(x, conv, down, what):
+    if x.dtype != torch.float32 or x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"{what}: x must be fp32 channels-last [S, H, W, C], got {tuple(x.shape)} {x.dtype}")
+    H, W = x.shape[1:3]
+    if not (_pow2(H) and _pow2(W)) or (down and (H < 2 or W < 2)):
+        raise ValueError(f"{what}: the grid {H} x {W} must be powers of two" + (", each at least 2" if down else ""))
+    if not isinstance(conv, nn.Conv2d):
+        raise ValueError(f"{what}: an nn.Conv2d is required, got {type(conv).__name__}")
+    stride, padding = ((2, 2), ((0, 0),)) if down else ((1, 1), ((1, 1), "same"))
+    if tuple(conv.kernel_size) != (3, 3) or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros":
+        raise ValueError(f"{what}: window {tuple(conv.kernel_size)}, dilation {tuple(conv.dilation)}, groups {conv.groups} (3 x 3, no dilation, one group)")
+    if tuple(conv.stride) != stride or conv.padding not in padding:
+        raise ValueError(f"{what}: stride {tuple(conv.stride)} with padding {conv.padding} (stride {stride[0]}, padding {padding[0][0]}: "
+                         f"{'the pad after the grid is part of the op' if down else 'on the nearest x2 grid'})")
+    N, C = conv.out_channels, conv.in_channels
+    if N % TILE or C % TILE:
+        raise ValueError(f"{what}: in_channels = {C} and out_channels = {N} must be multiples of {TILE}")
+    if x.shape[-1] != C:
+        raise ValueError(f"{what}: x has {x.shape[-1]} channels, the convolution takes {C}")
+    if conv.weight.dtype not in (torch.float32,) + HALF:
+        raise ValueError(f"{what}: weight dtype {conv.weight.dtype}")
+    for t in (x, conv.weight, conv.bias):
+        if t is not None:
+            require_device(t, what)
+    return _autocast_dtype(what)
+
+
+def conv_down(x, conv):
+    """diffusers' Downsample2D: y = conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2) + b, differentiable.  x: fp32 channels-last [S, H, W, C] on
+    the device, H and W powers of two >= 2; conv: a 3x3 nn.Conv2d with stride 2 and padding 0 (the pad after the grid is part of the op),
+    channels multiples of 128.  Returns fp32 [S, H/2, W/2, N].  Must run under fp16 / bf16 torch.autocast; anything else raises.  Saves
+    the 16-bit cast of x for the backward, which gives dx (fp32, bg_conv_down_dgrad), dW in the parameter's layout and db (fp32 for
+    fp32 masters, bg_conv_wgrad_geom).  Enqueues on the current stream, no host synchronisation."""
+    dt = _check_resample(x, conv, True, "conv_down")
+    return _Resample.apply(x, conv.weight, conv.bias, True, dt)
+
+
+def conv_up(x, conv):
+    """diffusers' Upsample2D: y = conv2d(F.interpolate(x, scale_factor=2, mode="nearest"), w, padding=1) + b, differentiable.  x: fp32
+    channels-last [S, H, W, C] on the device, H and W powers of two; conv: a 3x3 nn.Conv2d with stride 1 and padding 1, channels
+    multiples of 128.  Returns fp32 [S, 2H, 2W, N].  Must run under fp16 / bf16 torch.autocast; anything else raises.  Saves the 16-bit
+    cast of the LOW-resolution x (S*H*W*C elements, not four times that); the backward's dx is the 2 x 2 sum (bg_pool2x2_sum) of the
+    stride-1 data gradient on the 2H x 2W grid."""
+    dt = _check_resample(x, conv, False, "conv_up")
+    return _Resample.apply(x, conv.weight, conv.bias, False, dt)
+
+
+def _sampler_channels(c, what):
+    if c % TILE or c < TILE:
+        raise ValueError(f"{what}: c = {c} must be a multiple of {TILE}")
+
+
+class DeviceDownsample2D(nn.Module):
+    """diffusers' Downsample2D (a 3x3 convolution, stride 2, padded after the grid), parameter name `conv`: forward(x) = conv_down(x, conv)"""
+
+    def __init__(self, c, device=None, dtype=None):
+        super().__init__()
+        _sampler_channels(c, "DeviceDownsample2D")
+        self.conv = nn.Conv2d(c, c, 3, stride=2, padding=0, device=device, dtype=dtype)
+
+    def forward(self, x):
+        return conv_down(x, self.conv)
+
+
+class DeviceUpsample2D(nn.Module):
+    """diffusers' Upsample2D (nearest x2, then a 3x3 'same' convolution), parameter name `conv`: forward(x) = conv_up(x, conv)"""
+
+    def __init__(self, c, device=None, dtype=None):
+        super().__init__()
+        _sampler_channels(c, "DeviceUpsample2D")
+        self.conv = nn.Conv2d(c, c, 3, padding=1, device=device, dtype=dtype)
+
+    def forward(self, x):
+        return conv_up(x, self.conv)
+
+
+_SAMPLERS = {"downsamplers": DeviceDownsample2D, "upsamplers": DeviceUpsample2D}
+
+
+class DeviceBlock2D(nn.Module):
+    """diffusers' DownEncoderBlock2D / UpDecoderBlock2D with their keys: `resnets`, then optionally `downsamplers` or `upsamplers` (not
+    both).  forward(x): fp32 CHANNELS-LAST [S, H, W, cin], the resnets, then the sampler.  The children are taken as given (shared)."""
+
+    def __init__(self, resnets, downsamplers=None, upsamplers=None):
+        super().__init__()
+        if downsamplers is not None and upsamplers is not None:
+            raise ValueError("DeviceBlock2D: downsamplers or upsamplers, not both")
+        self.resnets = resnets if isinstance(resnets, nn.ModuleList) else nn.ModuleList(resnets)
+        for name, members in (("downsamplers", downsamplers), ("upsamplers", upsamplers)):
+            if members is not None:
+                setattr(self, name, members if isinstance(members, nn.ModuleList) else nn.ModuleList(members))
+
+    def forward(self, x):
+        for r in self.resnets:
+            x = r(x)
+        for name in _SAMPLERS:
+            for m in getattr(self, name, ()):
+                x = m(x)
+        return x
+
+
+def _is_sampler(m, name):
+    """exactly {conv.weight, conv.bias}, a 3x3 nn.Conv2d with the geometry of the list it sits in"""
+    if isinstance(m, _SAMPLERS[name]) or {k for k, _ in m.named_parameters()} != {"conv.weight", "conv.bias"}:
+        return False
+    c = getattr(m, "conv", None)
+    stride, padding = ((2, 2), (0, 0)) if name == "downsamplers" else ((1, 1), (1, 1))
+    return (isinstance(c, nn.Conv2d) and tuple(c.kernel_size) == (3, 3) and tuple(c.stride) == stride and c.padding == padding
+            and tuple(c.dilation) == (1, 1) and c.groups == 1 and c.padding_mode == "zeros" and c.in_channels == c.out_channels)
+
+
+def _swap_samplers(module):
+    for name, child in module.named_children():
+        if name in _SAMPLERS and isinstance(child, nn.ModuleList):
+            for i, m in enumerate(child):
+                if _is_sampler(m, name):
+                    child[i] = adopt(_SAMPLERS[name](m.conv.in_channels, device="meta"), m, "conv")
+        else:
+            _swap_samplers(child)
+
+
+def _is_block(m):
+    """`resnets` and at most one sampler list, nothing else, every member on the device path"""
+    kids = dict(m.named_children())
+    if isinstance(m, DeviceBlock2D) or "resnets" not in kids or not set(kids) <= {"resnets", *_SAMPLERS} or len(kids) > 2:
+        return False
+    if any(True for _ in m.parameters(recurse=False)) or not all(isinstance(k, nn.ModuleList) for k in kids.values()):
+        return False
+    return (all(isinstance(r, DeviceResnetBlock2D) for r in kids["resnets"])
+            and all(isinstance(s, _SAMPLERS[n]) for n in _SAMPLERS for s in kids.get(n, ())))
+
+
+def _wrap(m):
+    kids = dict(m.named_children())
+    return DeviceBlock2D(kids["resnets"], kids.get("downsamplers"), kids.get("upsamplers")).train(m.training)
+
+
+def _wrap_blocks(module):
+    for name, child in list(module.named_children()):
+        if _is_block(child):
+            setattr(module, name, _wrap(child))
+        elif not isinstance(child, DeviceBlock2D):
+            _wrap_blocks(child)
+
+
+def use_device_blocks(module):
+    """use_device_resnets(module), then: every member of a ModuleList named `downsamplers` / `upsamplers` whose only parameters are
+    conv.weight / conv.bias of a 3x3 nn.Conv2d with stride 2 / padding 0 (downsamplers) or stride 1 / padding 1 (upsamplers) becomes a
+    DeviceDownsample2D / DeviceUpsample2D that SHARES the conv, and every descendant whose children are `resnets` and at most one of the
+    two sampler lists (diffusers' DownEncoderBlock2D / UpDecoderBlock2D, vae._DownBlock2D / _UpBlock2D) becomes a DeviceBlock2D that
+    shares those lists.  Parameter objects and state_dict keys are unchanged; idempotent; launches nothing.  Modules with other
+    children -- a mid block with its attention, conv_in, conv_norm_out, conv_out -- stay what they are (a mid block's resnets are
+    swapped by use_device_resnets all the same).  Returns the module -- or, when `module` ITSELF is such a block, the DeviceBlock2D
+    around its children.  Converted blocks take and return CHANNELS-LAST fp32 [S, H, W, C]."""
+    use_device_resnets(module)
+    _swap_samplers(module)
+    _wrap_blocks(module)
+    return _wrap(module) if _is_block(module) else module

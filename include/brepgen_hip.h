@@ -335,7 +335,9 @@ int bg_masked_mse_bwd(const float* pred, const float* target, const uint8_t* row
  * No atomics, one writer per output element, fixed summation order: two calls give the same bits.  Arguments are checked before any
  * launch.  The DATA gradient has no entry of its own: it is the 'same' forward convolution of dy (cast to 16 bits by bg_im2col with a
  * 1x1 window and no norm) with the data-gradient pack of bg_conv_weight_pack, on bg_conv_gemm_fwd or, below that entry's 64-tile
- * rule, bg_im2col + bg_gemm_bias_act_fwd.  Not covered: stride-2 and up-sampling convolutions, conv_in / conv_out (3 and 6 channels). */
+ * rule, bg_im2col + bg_gemm_bias_act_fwd.  The stride-2 (Downsample2D) and up-sampling (Upsample2D) convolutions: "resampling
+ * convolutions in TRAINING" below.  Not covered: conv_in / conv_out (3 and 6 channels), the mid-block attention, the 1-D ResConvBlock and
+ * cubic resamplers, the posterior's backward. */
 
 /* dw [N, kh*kw*C] (tap-major / channel-minor: tap = ky*kw + kx, the layout of the forward's packed weight) and db [N] (may be NULL):
  *     dw[n, tap, c] = sum_{s,y,x} dy[s,y,x,n] * a[s, y + ky - kh/2, x + kx - kw/2, c]      db[n] = sum_{s,y,x} dy[s,y,x,n]
@@ -387,6 +389,59 @@ size_t bg_gn_act_bwd_workspace_bytes(int S, int P, int C, int G);
 int bg_gn_act_bwd(const float* da, const float* x, const float* stats, const float* gamma, const float* beta, const float* dskip,
                   float* dx, float* dgamma, float* dbeta, int S, int P, int C, int G, int act, void* workspace, size_t workspace_bytes,
                   bg_stream_t stream);
+
+/* ---- resampling convolutions in TRAINING (csrc/conv_train.hip): the backward of the VAEs' two 3 x 3 resampling convolutions,
+ *   DOWN  diffusers Downsample2D   y = conv2d(F.pad(x, (0, 1, 0, 1)), w, stride = 2)            H, W even, Ho = H / 2, Wo = W / 2
+ *         y[s,j,i,n] = b[n] + sum_{ky,kx,c} x[s, 2j + ky, 2i + kx, c] w[n,c,ky,kx]       a tap counts where 2j + ky < H and 2i + kx < W
+ *   UP    diffusers Upsample2D     y = conv2d(F.interpolate(x, scale_factor = 2, mode = "nearest"), w, padding = 1)   Ho = 2H, Wo = 2W
+ *         y[s,y,x,n] = b[n] + sum x[s, uy >> 1, ux >> 1, c] w[n,c,ky,kx],  uy = y + ky - 1, ux = x + kx - 1;  a tap counts where
+ *         0 <= uy < 2H and 0 <= ux < 2W -- tested BEFORE the shift
+ * whose forwards run on bg_im2col (stride / up / the before-padding) + bg_gemm_bias_act_fwd and bg_conv_gemm_fwd (up).  Activations are
+ * channels-last, grids powers of two, 16-bit operands BG_BF16 | BG_F16, N and C multiples of 128.  No atomics, one writer per output
+ * element, fixed summation order; arguments are checked before any launch.  UP's data gradient is the stride-1 'same' data gradient on
+ * the 2H x 2W grid (above) followed by bg_pool2x2_sum. */
+typedef enum { BG_CONV_SAME = 0, BG_CONV_DOWN2 = 1, BG_CONV_UP2 = 2 } bg_conv_geom;
+
+/* bg_conv_wgrad in one of three geometries: H x W is the grid of `a` [S, H, W, C], dy has M = S*Ho*Wo rows (Ho x Wo: H x W | H/2 x W/2 |
+ * 2H x 2W), dw is the forward pack's tap-major [N, 9C]:
+ *     DOWN2   dw[n,(ky,kx),c] = sum_{s,j,i} dy[s,j,i,n] a[s, 2j + ky, 2i + kx, c]        where 2j + ky < H and 2i + kx < W
+ *     UP2     dw[n,(ky,kx),c] = sum_{s,y,x} dy[s,y,x,n] a[s, uy >> 1, ux >> 1, c]        where 0 <= uy < 2H and 0 <= ux < 2W
+ * and db[n] = sum dy[., n].  The same kernel with one more loader: the row staged for output pixel m is one pixel of `a` computed as
+ * above, zero-filled in registers where the tap leaves the sample's grid -- never read, never taken from the neighbouring row or
+ * sample.  geom = BG_CONV_SAME forwards to bg_conv_wgrad (the same bits).  Otherwise bg_conv_wgrad's rules, and: window 3 x 3 only,
+ * BG_CONV_DOWN2 needs H, W >= 2 (BG_E_SHAPE); geom outside the enum is BG_E_ARG.  The split plan is lb_auto_split(M, N, 9C) with M
+ * from dy's grid; workspace as bg_conv_wgrad's formula with that split. */
+int bg_conv_wgrad_geom(const void* dy, int ld_dy, const void* a, int ld_a, void* dw, void* db, int S, int H, int W, int N, int C, int kh,
+                       int kw, int geom, int dtype, int out_dtype, int split, void* workspace, size_t workspace_bytes, bg_stream_t stream);
+size_t bg_conv_wgrad_geom_workspace_bytes(int S, int H, int W, int N, int C, int kh, int kw, int geom, int split);
+int bg_conv_wgrad_geom_split(int S, int H, int W, int N, int C, int kh, int kw, int geom);
+
+/* src: a 3 x 3 nn.Conv2d weight [N, C, 3, 3] (fp32, or 16-bit of `dtype`) -> either or both of
+ *     fwd    [N, 9C]      bg_conv_weight_pack's forward pack
+ *     down   9*C*N elements: the CLASS-ORDERED pack of bg_conv_down_dgrad, four dense blocks one after the other,
+ *            block k = [C, T_k * N], block[c, t, n] = src[n, c, tap_k[t]], with the taps (ky, kx) of
+ *            k = 0: (1,1) | k = 1: (1,0) (1,2) | k = 2: (0,1) (2,1) | k = 3: (0,0) (0,2) (2,0) (2,2)     (blocks start at C*N * {0, 1, 3, 5})
+ * 16-bit of `dtype`, round to nearest even.  N % 32 == 0, C % 32 == 0; dense, 16-byte aligned.  One launch. */
+int bg_conv_weight_pack_down(const void* src, int src_dtype, int N, int C, void* fwd, void* down, int dtype, bg_stream_t stream);
+
+/* DOWN's data gradient: dx fp32 [S, H, W, C] from dy 16-bit [S, H/2, W/2, N] (pixel stride ld_dy >= N, a multiple of 8) and the
+ * class-ordered pack:
+ *     dx[s,iy,ix,c] = sum dy[s, (iy - ky) / 2, (ix - kx) / 2, n] w[n,c,ky,kx]   over ky in {1} for odd iy, {0, 2} for even iy, likewise kx,
+ *                                                                               wherever iy - ky >= 0 and ix - kx >= 0
+ * The four parity classes of (iy, ix) take 1, 2, 2 and 4 taps: 9 tap-products per four input pixels, the forward's work (no
+ * zero-stuffed dy).  One gather launch writes the three multi-tap class operands [M, T_k * N] (M = S*H/2*W/2; a neighbour before the
+ * sample's first row / column is zeros by an index test; class 0's operand is dy itself), four bg_gemm_bias_act_fwd launches fill a
+ * class-major fp32 buffer [4][M][C], one 16-byte pass interleaves it into dx: every element of dx is written exactly once.  H, W
+ * powers of two >= 2, S >= 1, N and C multiples of 128 (BG_E_SHAPE).  Workspace: the three operands and the buffer, each rounded up to
+ * 256 bytes (2 * al(4MN) + al(8MN) + al(16MC) bytes); 0 for rejected shapes. */
+size_t bg_conv_down_dgrad_workspace_bytes(int S, int H, int W, int N, int C);
+int bg_conv_down_dgrad(const void* dy, int ld_dy, const void* pack, float* dx, int S, int H, int W, int N, int C, int dtype, void* workspace,
+                       size_t workspace_bytes, bg_stream_t stream);
+
+/* y[s,Y,X,c] = (u[s,2Y,2X,c] + u[s,2Y,2X+1,c]) + (u[s,2Y+1,2X,c] + u[s,2Y+1,2X+1,c]) (+ add[s,Y,X,c]), fp32, in that association:
+ * the backward of nearest x2 up-sampling.  u [S, 2H, 2W, C], y and add (may be NULL: e.g. a skip gradient) [S, H, W, C], dense,
+ * 16-byte aligned, C % 4 == 0.  One launch, 16-byte accesses. */
+int bg_pool2x2_sum(const float* u, const float* add, float* y, int S, int H, int W, int C, bg_stream_t stream);
 
 /* QKV projection with the LayerNorm fold + self-attention in ONE launch (csrc/qkv_attn.hip): sequences of an even length
  * N <= 64, all B of them equally long; key_pad (may be NULL) as bg_attn_fwd's.  x_hi [B*N, 768] raw 16-bit rows, w_qkv [2304, 768] /
